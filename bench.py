@@ -346,6 +346,29 @@ def projected_from_rank_share(world, ne, L, measured_ms):
         return None
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: size limit of the .npy files together
+
+
+def dump_outputs(eng, grid, outdir):
+    """Write the prognostic state in instance 0 -- what a caller of step_ars343 receives -- as outdir/<name>.npy in float64, one row per
+    interior node column of every patch, in patch order: U, V, rhotheta, rho [columns][L] and W [columns][L + 1].  When all columns
+    would exceed DUMP_BYTES, a sample of them is written; it is drawn with seed 0 from the column count alone, so that two builds run
+    with the same arguments write the same columns.  Returns (columns written, columns in the state)."""
+    import numpy as np
+    L = grid.L
+    state = eng.download_state(0)
+    node = np.concatenate([state[p][0][:, 1:-1, 1:-1].reshape(5, -1, L) for p in range(len(grid.patches))], axis=1)
+    w = np.concatenate([state[p][1][3, 1:-1, 1:-1].reshape(-1, L + 1) for p in range(len(grid.patches))], axis=0)
+    ncol = w.shape[0]
+    keep = (DUMP_BYTES - 5 * 4096) // (8 * (5 * L + 1))      # (4096 B per file for the .npy header)
+    cols = np.arange(ncol) if ncol <= keep else np.sort(np.random.default_rng(0).choice(ncol, keep, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    for name, c in (("U", 0), ("V", 1), ("rhotheta", 2), ("rho", 4)):
+        np.save(os.path.join(outdir, name + ".npy"), node[c][cols])
+    np.save(os.path.join(outdir, "W.npy"), w[cols])
+    return len(cols), ncol
+
+
 def self_launch(n):
     """Run this script as n ranks under torch.distributed.run (127.0.0.1 rendezvous on a free port) and return the launcher's exit code.
     stdout of the ranks passes through (rank 0 prints the one JSON line), stderr too.  Nothing in this process has initialised the GPU."""
@@ -389,7 +412,14 @@ def main():
     ap.add_argument("--parity-steps", type=int, default=3,
                     help="N > 1: after the timing, all ranks and a single-rank engine on rank 0 step this many times from the initial state and "
                          "rank 0's patches are compared bit for bit (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the state they produced as DIR/<name>.npy (float64, at most 64 MB: a fixed sample of "
+                         "columns when the state is larger; see dump_outputs).  One rank only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -554,6 +584,9 @@ def main():
     barrier()
     wall = time.perf_counter() - t0
     unique_after_timed = eng.info(13)      # data instances in node-unique form when the timed region ended
+    if args.dump_outputs:
+        written, ncol = dump_outputs(eng, grid, args.dump_outputs)
+        sys.stderr.write("bench: state after the %d timed steps written to %s (%d of %d columns)\n" % (args.steps, args.dump_outputs, written, ncol))
     # per-kernel device time: the same K steps again with HIP events around every launch on the
     # engine's stream (kept out of the timed region: the event markers cost a few % of wall time)
     eng.profile_enable(True)
