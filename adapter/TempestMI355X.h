@@ -8,7 +8,8 @@
 //                                the GPU; the host arrays (instance 0) are refreshed per MI355XEngine's host
 //                                synchronisation policy (every step by default).
 //   HeldSuarezPhysicsMI355X /    the column physics WorkflowProcesses on the device, sharing that policy.
-//   KesslerPhysicsMI355X
+//   KesslerPhysicsMI355X /
+//   DCMIPPhysicsMI355X
 //   HorizontalDynamicsMI355X /   parity mode: the reference's own TimestepScheme, Grid::CopyData,
 //   VerticalDynamicsMI355X       LinearCombineData and ApplyDSS keep running on the host arrays; every
 //                                call uploads the instances it reads and downloads the one it writes.
@@ -850,6 +851,30 @@ private:
 };
 
 ///	<summary>
+///		The device's accumulated precipitation (UserData2D item 0, "PRECT") added to the patches' host arrays and reset on the
+///		device, so that the host array keeps the running total (the column-physics processes below call it on every refresh).
+///	</summary>
+inline void MI355XFlushPrecipitation(Model & model) {
+	MI355XEngine & eng = MI355XEngine::For(model);
+	Grid * pGrid = model.GetGrid();
+	for (int n = 0; n < pGrid->GetActivePatchCount(); n++) {
+		GridPatch * pPatch = pGrid->GetActivePatch(n);
+		DataArray3D<double> & dataUserData2D = pPatch->GetUserData2D();
+		if (dataUserData2D.GetRows() == 0) {
+			_EXCEPTIONT("Insufficient entries in UserData2D");
+		}
+		// the device accumulator is added to the host array and reset, so that the host array keeps the running total
+		const PatchBox & box = pPatch->GetPatchBox();
+		DataArray2D<double> dAcc(box.GetATotalWidth(), box.GetBTotalWidth());
+		MI355XEngine::Check(tmx_download_precipitation(eng.Handle(), pPatch->GetPatchIndex(), &(dAcc[0][0]), 1));
+		for (int i = box.GetAInteriorBegin(); i < box.GetAInteriorEnd(); i++)
+		for (int j = box.GetBInteriorBegin(); j < box.GetBInteriorEnd(); j++)
+			dataUserData2D[0][i][j] += dAcc[i][j];
+	}
+}
+
+
+///	<summary>
 ///		KesslerPhysics (test/dcmip2016/KesslerPhysics.h) on the device: same constructor, same attachment.  The
 ///		accumulated precipitation (UserData2D item 0, KesslerPhysics.cpp:234) is kept on the device and written to the
 ///		patch's UserData2D by FlushPrecipitation() (called whenever the host copy of the state is refreshed here).
@@ -859,24 +884,7 @@ public:
 	KesslerPhysicsMI355X(Model & model, const Time & timeFrequency) :
 		WorkflowProcess(model, timeFrequency), m_fInputsSet(false) { }
 
-	void FlushPrecipitation() {
-		MI355XEngine & eng = MI355XEngine::For(m_model);
-		Grid * pGrid = m_model.GetGrid();
-		for (int n = 0; n < pGrid->GetActivePatchCount(); n++) {
-			GridPatch * pPatch = pGrid->GetActivePatch(n);
-			DataArray3D<double> & dataUserData2D = pPatch->GetUserData2D();
-			if (dataUserData2D.GetRows() == 0) {
-				_EXCEPTIONT("Insufficient entries in UserData2D");
-			}
-			// the device accumulator is added to the host array and reset, so that the host array keeps the running total
-			const PatchBox & box = pPatch->GetPatchBox();
-			DataArray2D<double> dAcc(box.GetATotalWidth(), box.GetBTotalWidth());
-			MI355XEngine::Check(tmx_download_precipitation(eng.Handle(), pPatch->GetPatchIndex(), &(dAcc[0][0]), 1));
-			for (int i = box.GetAInteriorBegin(); i < box.GetAInteriorEnd(); i++)
-			for (int j = box.GetBInteriorBegin(); j < box.GetBInteriorEnd(); j++)
-				dataUserData2D[0][i][j] += dAcc[i][j];
-		}
-	}
+	void FlushPrecipitation() { MI355XFlushPrecipitation(m_model); }
 
 	static void FlushHook(void * pThis) { static_cast<KesslerPhysicsMI355X *>(pThis)->FlushPrecipitation(); }
 
@@ -899,6 +907,50 @@ public:
 	}
 
 private:
+	bool m_fInputsSet;
+};
+
+///	<summary>
+///		DCMIPPhysics (test/dcmip2016/DCMIPPhysics.h) on the device: same constructor (model, timeFrequency, iTestCase,
+///		iPBLType, iPrecType), same attachment.  The first Perform registers the latitude, node angles, level and interface
+///		heights of every patch; the accumulated precipitation is handled as for KesslerPhysicsMI355X.
+///	</summary>
+class DCMIPPhysicsMI355X : public WorkflowProcess {
+public:
+	DCMIPPhysicsMI355X(Model & model, const Time & timeFrequency, int iTestCase, int iPBLType, int iPrecType) :
+		WorkflowProcess(model, timeFrequency), m_iTestCase(iTestCase), m_iPBLType(iPBLType), m_iPrecType(iPrecType), m_fInputsSet(false) { }
+
+	void FlushPrecipitation() { MI355XFlushPrecipitation(m_model); }
+
+	static void FlushHook(void * pThis) { static_cast<DCMIPPhysicsMI355X *>(pThis)->FlushPrecipitation(); }
+
+	virtual void Perform(const Time & time) {
+		MI355XEngine & eng = MI355XEngine::For(m_model);
+		tmx_engine * pEngine = eng.Handle();
+		Grid * pGrid = m_model.GetGrid();
+		if (!m_fInputsSet) {
+			const double dEarthRadius = m_model.GetPhysicalConstants().GetEarthRadius();
+			for (int n = 0; n < pGrid->GetActivePatchCount(); n++) {
+				GridPatch * pPatch = pGrid->GetActivePatch(n);
+				const PatchBox & box = pPatch->GetPatchBox();
+				std::vector<double> dA(box.GetATotalWidth()), dB(box.GetBTotalWidth());
+				for (int i = 0; i < box.GetATotalWidth(); i++) dA[i] = pPatch->GetANode(i);
+				for (int j = 0; j < box.GetBTotalWidth(); j++) dB[j] = pPatch->GetBNode(j);
+				MI355XEngine::Check(tmx_set_patch_level_heights(pEngine, pPatch->GetPatchIndex(), &(pPatch->GetZLevels()[0][0][0])));
+				MI355XEngine::Check(tmx_set_patch_dcmip_inputs(pEngine, pPatch->GetPatchIndex(), &(pPatch->GetLatitude()[0][0]),
+					&dA[0], &dB[0], &(pPatch->GetZInterfaces()[0][0][0]), dEarthRadius));
+			}
+			m_fInputsSet = true;
+		}
+		eng.SetFlushHook(&DCMIPPhysicsMI355X::FlushHook, this);
+		eng.EnsureDevice();
+		MI355XEngine::Check(tmx_physics_dcmip2016(pEngine, 0, m_timeFrequency.GetSeconds(), m_iTestCase, m_iPBLType, m_iPrecType));
+		eng.DeviceModified(false, false);
+		WorkflowProcess::Perform(time);
+	}
+
+private:
+	int m_iTestCase, m_iPBLType, m_iPrecType;
 	bool m_fInputsSet;
 };
 

@@ -346,6 +346,24 @@ int tmx_set_patch_level_heights(tmx_engine * e, int patch, const double * z_leve
 int tmx_physics_kessler(tmx_engine * e, int instance, double dt);
 int tmx_download_precipitation(tmx_engine * e, int patch, double * prect, int reset);
 
+/* DCMIP2016 column physics of the tropical cyclone (test 2) and the moist baroclinic wave (test 1): DCMIPPhysics::Perform
+ * (test/dcmip2016/DCMIPPhysics.cpp:156-409) around SUBROUTINE DCMIP2016_PHYSICS (test/dcmip2016/interface/dcmip_physics_z_v1.f90),
+ * a WorkflowProcess like Kessler's (Model.cpp:470-481).  Needs n_tracers >= 3 with tracers 0,1,2 = RhoQv, RhoQc, RhoQr
+ * (TropicalCycloneTest.cpp, BaroclinicWaveUMJSTest.cpp); further tracers are left as they are.
+ * tmx_set_patch_dcmip_inputs: per owned patch latitude [na][nb] = GridPatch::GetLatitude(), a_nodes [na] / b_nodes [nb] =
+ *   GridPatch::GetANode(i) / GetBNode(j), z_interfaces [na][nb][L+1] = GetZInterfaces() (DCMIPPhysics.cpp:202-203, :272-279), and
+ *   earth_radius = PhysicalConstants::GetEarthRadius() (the same for all patches).  The level heights come through
+ *   tmx_set_patch_level_heights.  The host forms each column's covector transform coefficients (CubedSphereTrans.cpp:549-729)
+ *   and the test-1 surface temperature here.
+ * tmx_physics_dcmip2016: Perform on `instance` with dDeltaT = dt, m_iTestCase = test (1, 2, 3), m_iPBLType = pbl_type (0: Reed-
+ *   Jablonowski, 1: Bryan) and m_iPrecType = prec_type (0: Kessler, 1: Reed-Jablonowski); updates U, V, rho*theta, rho and the three
+ *   tracer densities and adds precl * dt to the accumulated precipitation (UserData2D item 0, read with tmx_download_precipitation).
+ *   TMX_ERR_UNSUPPORTED for the shallow-water set (the engine keeps theta on levels; the reference throws for theta on interfaces,
+ *   DCMIPPhysics.cpp:180-182). */
+int tmx_set_patch_dcmip_inputs(tmx_engine * e, int patch, const double * latitude, const double * a_nodes, const double * b_nodes,
+	const double * z_interfaces, double earth_radius);
+int tmx_physics_dcmip2016(tmx_engine * e, int instance, double dt, int test, int pbl_type, int prec_type);
+
 /* Wait for the engine's stream; reports a deferred TMX_ERR_SINGULAR from column solves. */
 int tmx_sync(tmx_engine * e);
 
@@ -538,6 +556,12 @@ int tmx_debug_pivot_stats(tmx_engine * e, int enable, unsigned long long out[2])
  * executed decisions, and returns -1000 - n when n reads through the instance maps would not have found the reference's value
  * (0: sound); share = 2 is the check's negative control: every share accepted and no copy-on-write. */
 int tmx_debug_program_copies(int scheme, int mode, int steps, int share, int * copies, int * shared);
+/* Host logic of tmx_set_patch_dcmip_inputs, for tests: the covector coefficients of a node at angles (alpha, beta) of `panel`,
+ * out[11] = {lon <- u_a, lon <- u_b, lat <- u_a, lat <- u_b, cos(lat) factor of lon; cos(lat) divisor of lon, u_a <- lon, u_a <- lat,
+ * u_b <- lon, u_b <- lat; 0}: u_lon = (out0 u_a + out1 u_b) out4, u_lat = out2 u_a + out3 u_b; l = u_lon / out5, u_a = out6 l + out7 u_lat,
+ * u_b = out8 l + out9 u_lat.  tmx_debug_dcmip_tsurf: the test-1 surface temperature at latitude lat. */
+int tmx_debug_dcmip_node_coefficients(int panel, double alpha, double beta, double * out);
+int tmx_debug_dcmip_tsurf(double lat, double * out);
 
 /* Per-kernel device time accumulated with HIP events on the engine's stream since the last reset.
  * kernel ids: TMX_K_* below.  Profiling is off by default (no events recorded). */

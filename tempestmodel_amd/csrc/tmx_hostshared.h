@@ -94,4 +94,5 @@ void interp_orphan(tmx_engine * e);      // output-interpolation plans of an eng
 // defined in tmx_host.hip
 int check_reference_state(tmx_engine * e);
 int ensure_layout(tmx_engine * e);
+int column_physics_levels(tmx_engine * e);
 struct LoopbackGroup;

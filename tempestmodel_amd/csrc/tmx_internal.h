@@ -79,7 +79,7 @@ struct KParams {
 };
 
 struct PatchInfo {
-	bool defined = false, halo_set = false, geom_set = false, metric_ok = false, rayleigh_set = false, physics_set = false, ref_set = false, zlev_set = false;
+	bool defined = false, halo_set = false, geom_set = false, metric_ok = false, rayleigh_set = false, physics_set = false, ref_set = false, zlev_set = false, dcmip_set = false;
 	int panel = -1, nea = 0, neb = 0, na = 0, nb = 0, owner = 0;
 	int nbp[8];
 	int elem_base = -1;                      // first local element, -1 if not owned
@@ -241,6 +241,10 @@ struct tmx_engine {
 	// Kessler microphysics (tmx_physics_kessler): level heights [L][NS], accumulated precipitation [NS], column work arrays [8][L][NS]
 	std::vector<double> h_zlev; bool zlev_dirty = false;
 	double * d_zlev = nullptr, * d_prect = nullptr, * d_kes = nullptr;
+	// DCMIP2016 column physics (tmx_physics_dcmip2016, tmx_dcmip.hip): per column [TMX_DC_NCOEF] covector coefficients + test-1 surface
+	// temperature, interface heights [L+1][NS], column work arrays [TMX_DC_NW][L][NS] (allocated at first use)
+	std::vector<double> h_dcmip, h_zint; bool dcmip_dirty = false; double dcmip_radius = 0.0;
+	double * d_dcmip = nullptr, * d_zint = nullptr, * d_dcw = nullptr;
 	size_t hbm_bytes = 0;
 
 	// comm
@@ -300,7 +304,7 @@ struct tmx_engine {
 	std::vector<StepGraph> graphs;
 	// switches that used to be read from the environment at their point of use (tmx_set_option / tmx_options_from_environment)
 	int opt_no_split = 0, opt_metric_stored = 0, opt_tracer_lincomb_pass = 0, opt_udv_separate = 0, opt_vx_fused = 0, opt_skip_exchange = 0,
-	    opt_no_exchange_overlap = 0, opt_kessler_column = 0, opt_vi_sparse = 1, opt_vt_column = 0, opt_vt_explicit_v1 = 0, opt_vt_walk = -1000, opt_vite_walk = -1000, opt_vx_walk = -1000, opt_vt_lanes = 16,
+	    opt_no_exchange_overlap = 0, opt_kessler_column = 0, opt_dcmip_lds = 0, opt_vi_sparse = 1, opt_vt_column = 0, opt_vt_explicit_v1 = 0, opt_vt_walk = -1000, opt_vite_walk = -1000, opt_vx_walk = -1000, opt_vt_lanes = 16,
 	    opt_vt_lw8 = -1, opt_vt_nr = 0, opt_vt_rows = 1, opt_vi_cpw = 0;
 	int lu_fma = 1;                          // option "lu_fma": 1 = band-LU updates as fused multiply-adds (OpenBLAS, MKL's FMA paths), 0 = multiply + subtract (tmx_lu_select.hip)
 	int opt_h_walk_udiff = 2;                // the walk applies the horizontal uniform diffusion itself (element-major uniform-diffusion configurations): 1; 2 (default) V.StepExplicit's U,V part too; 0 = k_uniform_diffusion / k_v_explicit as passes of their own
@@ -395,6 +399,13 @@ void tmxk_p2p_signal_wait(tmx_engine * e, hipStream_t s, int buf, unsigned long 
 void tmxk_rayleigh(tmx_engine * e, const KParams & p, double * x, double dt, const double * xs = nullptr, size_t NSS = 0, const int * ucd = nullptr);
 void tmxk_held_suarez(tmx_engine * e, const KParams & p, double * x, const double * surf, double dt, const double * xs = nullptr, size_t NSS = 0, const int * ucd = nullptr);
 void tmxk_kessler(tmx_engine * e, const KParams & p, double * x, double dt);
+// DCMIP2016_PHYSICS per column (tmx_k_physics.hip).  Column inputs [TMX_DC_NCOEF][NS]: RLL-from-ABP coefficients (lon <- a, lon <- b,
+// lat <- a, lat <- b, cos(lat) factor of lon), ABP-from-RLL (cos(lat) divisor of lon, a <- lon, a <- lat, b <- lon, b <- lat), Tsurf of test 1
+enum { DC_RA0 = 0, DC_RA1, DC_RB0, DC_RB1, DC_RCOS, DC_ADIV, DC_AA0, DC_AA1, DC_AB0, DC_AB1, DC_TSURF1, TMX_DC_NCOEF };
+#define TMX_DC_NW 20
+// threads = 64 columns; lds: the six Thomas coefficient arrays of a column in LDS (option dcmip_lds, where 6 * L * 64 doubles fit: tmxk_dcmip_lds_bytes != 0)
+size_t tmxk_dcmip_lds_bytes(int L);
+void tmxk_dcmip(tmx_engine * e, const KParams & p, double * x, double dt, int test, int pbl, int prec, double earth_radius, bool lds);
 // tracers (rows H8 / V8)
 void tmxk_h_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * xbase, double * xup, double dt,
 	int nterms = 0, const double * const * src = nullptr, const double * coef = nullptr, int premul = 0, const double * xin_uv = nullptr);

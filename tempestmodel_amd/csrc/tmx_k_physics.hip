@@ -389,5 +389,271 @@ void tmxk_kessler(tmx_engine * e, const KParams & p, double * x, double dt) {
 	hipLaunchKernelGGL(k_kessler, dim3((p.ncol + 255) / 256), dim3(256), 0, e->stream, p, x, (const double *)e->d_zlev, e->d_kes, e->d_prect, dt, gamma, pscal);
 }
 
+// Column physics of the DCMIP2016 tropical cyclone and moist baroclinic wave: DCMIPPhysics::Perform (test/dcmip2016/DCMIPPhysics.cpp:156-409)
+// around SUBROUTINE DCMIP2016_PHYSICS (test/dcmip2016/interface/dcmip_physics_z_v1.f90:55-409), Lorenz staggering /
+// FORMULATION_RHOTHETA_PI, tracers 0,1,2 = RhoQv, RhoQc, RhoQr (the others are not touched).  One lane per stored column, 64 columns per
+// workgroup; the recurrences of the column (Kessler's sub-cycles, the surface pressure sum, the Thomas sweep of the boundary-layer
+// diffusion) run in k.  The column's arrays live in HBM work arrays [DW_*][L][NS] (coalesced across lanes), the six Thomas
+// coefficient arrays in LDS [6][L][64] where they fit (LDS = true).  The arithmetic is the Fortran's as the reference's build compiles
+// it (amdflang -O3 on the host: no FMA, constant sub-expressions folded in the order of evaluation, x**2 = x * x, x**(rair/cpair)
+// and x**(cpair/(cpair-rair)) calls of pow with the exponents 0x3FD2492492492492 and 1.4); exp / pow are glibc's (tmx_refmath.h).
+// The covector coefficients and the test-1 surface temperature come from the host (tmx_dcmip.hip).
+enum { DW_U = 0, DW_V, DW_P, DW_QV, DW_QC, DW_QR, DW_RHOD, DW_RHOM, DW_QSV, DW_T, DW_TH, DW_PK, DW_PC, DW_VEL, DW_EM, DW_EE, DW_FU, DW_FV, DW_FT, DW_FQ, DW_NF };
+static_assert(DW_NF == TMX_DC_NW, "work array count");
+
+template <int PBL, int PREC, bool LDS>
+__global__ __launch_bounds__(64) void k_dcmip(KParams p, double * __restrict__ x, const double * __restrict__ zlev, const double * __restrict__ zint,
+	const double * __restrict__ cf, double * __restrict__ w, double * __restrict__ prect, double dt, int test, double gamma, double pscal,
+	double kappa, double a)
+{
+	extern __shared__ double dsm[];
+	const int L = p.L;
+	const size_t NS = (size_t)p.NS;
+	const int tx = threadIdx.x;
+	const int col = blockIdx.x * 64 + tx;
+	if (col >= p.ncol) return;      // (no barriers below: every lane works on its own column)
+#define DW(f, k) w[((size_t)(f) * L + (k)) * NS + col]
+#define DT(f, k) (*(LDS ? &dsm[((size_t)(f) * L + (k)) * 64 + tx] : &DW(DW_EM + (f), k)))
+#define ZL(k) zlev[(size_t)(k) * NS + col]
+#define ZI(k) zint[(size_t)(k) * NS + col]
+	// dcmip_physics_z_v1.f90:113-157
+	const double gravit = 9.80616, rair = 287.0, cpair = 1004.5, latvap = 2.5e6, rh2o = 461.5;
+	const double epsilo = rair / rh2o, zvir = (rh2o / rair) - 1.0;
+	const double C = 0.0011, T0 = 273.16, e0 = 610.78, rhow = 1000.0, Cd0 = 0.0007, Cd1 = 0.000065, Cm = 0.002, v20 = 20.0;
+	const double p0 = 100000.0, pbltop = 85000.0, zpbltop = 1000.0, pblconst = 10000.0, vkappa = 0.4;
+	const double rdcp = 0x1.2492492492492p-2;      // rair/cpair as folded by the compiler
+	const double cpcv = 1.4;                       // cpair/(cpair-rair)
+	const double ra0 = cf[DC_RA0 * NS + col], ra1 = cf[DC_RA1 * NS + col], rb0 = cf[DC_RB0 * NS + col], rb1 = cf[DC_RB1 * NS + col], rcos = cf[DC_RCOS * NS + col];
+	// ---- DCMIPPhysics.cpp:255-336: the column's inputs; dcmip_physics_z_v1.f90:221-230: moist density, specific humidity, T ----
+	for (int k = 0; k < L; k++) {
+		const double rho = x[(size_t)TMX_SLAB_R(L, k) * NS + col], rt = x[(size_t)TMX_SLAB_T(L, k) * NS + col];
+		const double t0 = x[(size_t)TMX_SLAB_Q(L, 0, k) * NS + col], t1 = x[(size_t)TMX_SLAB_Q(L, 1, k) * NS + col], t2 = x[(size_t)TMX_SLAB_Q(L, 2, k) * NS + col];
+		const double thv = rt / rho;
+		const double ua = x[(size_t)TMX_SLAB_U(L, k) * NS + col] / a, ub = x[(size_t)TMX_SLAB_V(L, k) * NS + col] / a;
+		DW(DW_U, k) = (ra0 * ua + ra1 * ub) * rcos;
+		DW(DW_V, k) = rb0 * ua + rb1 * ub;
+		const double rhod = rho - t0 - t1 - t2;
+		const double pr = pscal * tmx_ref_exp(tmx_ref_log(rho * thv) * gamma);      // PhysicalConstants::PressureFromRhoTheta
+		double qv = t0 / rho; if (qv < 0.0) qv = 0.0;
+		double qc = t1 / rho; if (qc < 0.0) qc = 0.0;
+		double qr = t2 / rho; if (qr < 0.0) qr = 0.0;
+		const double rhom = rhod * (1.0 + qv);
+		DW(DW_P, k) = pr; DW(DW_QV, k) = qv; DW(DW_QC, k) = qc; DW(DW_QR, k) = qr; DW(DW_RHOD, k) = rhod;
+		DW(DW_RHOM, k) = rhom;
+		DW(DW_QSV, k) = qv * rhod / rhom;
+		DW(DW_T, k) = pr / (rhom * rair * (1.0 + zvir * qv));
+	}
+	double precl = 0.0;
+	if (PREC == 1) {
+		// ---- :235-255 Reed-Jablonowski large-scale condensation ----
+		for (int k = 0; k < L; k++) {
+			const double dz = ZI(k + 1) - ZI(k);
+			const double pk_ = DW(DW_P, k);
+			double t = DW(DW_T, k), qsv = DW(DW_QSV, k);
+			const double qsat = epsilo * e0 / pk_ * tmx_ref_exp(-(latvap / rh2o) * ((1.0 / t) - (1.0 / T0)));
+			if (qsv > qsat) {
+				const double rhom = DW(DW_RHOM, k), rhod = DW(DW_RHOD, k);
+				const double deltaqsv = (qsv - qsat) / (1.0 + (latvap / cpair) * epsilo * latvap * qsat / (rair * (t * t)));
+				t = t + latvap / cpair * deltaqsv;
+				qsv = qsv - deltaqsv;
+				precl = precl + deltaqsv * rhom * dz / (dt * rhow);
+				const double qv = qsv / (1.0 - qsv);
+				const double rhom_n = rhod / (1.0 - qsv);
+				DW(DW_T, k) = t; DW(DW_QSV, k) = qsv; DW(DW_QV, k) = qv; DW(DW_RHOM, k) = rhom_n;
+				DW(DW_P, k) = rhom_n * rair * t * (1.0 + zvir * qv);
+			}
+		}
+	} else {
+		// ---- :260-292 Kessler: exner and theta, SUBROUTINE KESSLER (kessler.f90:64-185, the level functions of k_kessler_tile), back ----
+		const double rhod0 = DW(DW_RHOD, 0);
+		double dt_max = dt, z_prev = 0.0; float vel_prev = 0.0f;
+		for (int k = 0; k < L; k++) {
+			const double pk_ = tmx_ref_pow(DW(DW_P, k) / p0, rdcp);
+			DW(DW_PK, k) = pk_;
+			DW(DW_TH, k) = DW(DW_T, k) / pk_;
+			const KesPcVel pv_ = kes_level_pc_vel(pk_, DW(DW_QR, k), DW(DW_RHOD, k), rhod0);
+			DW(DW_PC, k) = (double)pv_.pc; DW(DW_VEL, k) = (double)pv_.vel;
+			const double z = ZL(k);
+			if (k > 0 && vel_prev != 0.0f) { const double c = 0.8 * (z - z_prev) / (double)vel_prev; dt_max = (dt_max < c) ? dt_max : c; }
+			vel_prev = pv_.vel; z_prev = z;
+		}
+		const int rainsplit = (int)ceil(dt / dt_max);
+		const double dt0 = dt / (double)rainsplit;
+		const double rhoqr = 1000.0;
+		for (int nt = 1; nt <= rainsplit; nt++) {
+			double qr_k = DW(DW_QR, 0), rhod_k = DW(DW_RHOD, 0), z_k = ZL(0);
+			float vel_k = (float)DW(DW_VEL, 0), r_k = (float)(0.001 * rhod_k);
+			precl = precl + rhod_k * qr_k * (double)vel_k / rhoqr;
+			double z_km = 0.0;
+			for (int k = 0; k < L; k++) {
+				float sed;
+				double qr_n = 0.0, rhod_n = 0.0, z_n = 0.0; float vel_n = 0.0f, r_n = 0.0f;
+				if (k < L - 1) {
+					qr_n = DW(DW_QR, k + 1); rhod_n = DW(DW_RHOD, k + 1); z_n = ZL(k + 1);
+					vel_n = (float)DW(DW_VEL, k + 1); r_n = (float)(0.001 * rhod_n);
+					sed = (float)(dt0 * ((double)r_n * qr_n * (double)vel_n - (double)r_k * qr_k * (double)vel_k) / ((double)r_k * (z_n - z_k)));
+				} else {
+					sed = (float)(-dt0 * qr_k * (double)vel_k / ((double)0.5f * (z_k - z_km)));
+				}
+				KesLevel lv; lv.th = DW(DW_TH, k); lv.qv = DW(DW_QV, k); lv.qc = DW(DW_QC, k); lv.qr = qr_k; lv.vel = vel_k;
+				lv = kes_sweep_level(lv, DW(DW_PK, k), DW(DW_PC, k), rhod_k, rhod0, sed, dt0, nt != rainsplit);
+				DW(DW_TH, k) = lv.th; DW(DW_QV, k) = lv.qv; DW(DW_QC, k) = lv.qc; DW(DW_QR, k) = lv.qr;
+				if (nt != rainsplit) DW(DW_VEL, k) = (double)lv.vel;
+				z_km = z_k;
+				qr_k = qr_n; rhod_k = rhod_n; z_k = z_n; vel_k = vel_n; r_k = r_n;
+			}
+		}
+		precl = precl / (double)rainsplit;
+		for (int k = 0; k < L; k++) {
+			const double qv = DW(DW_QV, k), rhod = DW(DW_RHOD, k);
+			const double qsv = qv / (1.0 + qv);
+			const double rhom = rhod / (1.0 - qsv);
+			const double thetav = DW(DW_TH, k) * (1.0 + zvir * qv);
+			const double pr = p0 * tmx_ref_pow(rhom * rair * thetav / p0, cpcv);
+			DW(DW_QSV, k) = qsv; DW(DW_RHOM, k) = rhom; DW(DW_P, k) = pr;
+			DW(DW_T, k) = pr / (rhom * rair * (1.0 + zvir * qv));
+		}
+	}
+	if (test != 3) {
+		// ---- :303-311 drag coefficient; :314-353 eddy diffusivities (formed where the sweep needs them; interface 1 reads p(1)
+		// before the surface flux changes it) ----
+		const double u1 = DW(DW_U, 0), v1 = DW(DW_V, 0);
+		const double wind = sqrt(u1 * u1 + v1 * v1);
+		const double Cd = (wind < v20) ? Cd0 + Cd1 * wind : Cm;
+		const double za = ZL(0);
+		const double p1_old = DW(DW_P, 0);
+		// ---- :360-374 surface fluxes ----
+		const double Tsurf = (test == 1) ? cf[DC_TSURF1 * NS + col] : 302.15;
+		double ps = 0.0;
+		for (int k = 0; k < L; k++) ps = ps + gravit * DW(DW_RHOM, k) * (ZI(k + 1) - ZI(k));
+		const double qsats = epsilo * e0 / ps * tmx_ref_exp(-latvap / rh2o * ((1.0 / Tsurf) - (1.0 / T0)));
+		{
+			const double qsv1 = (DW(DW_QSV, 0) + C * wind * qsats * dt / za) / (1.0 + C * wind * dt / za);
+			const double t1 = (DW(DW_T, 0) + C * wind * Tsurf * dt / za) / (1.0 + C * wind * dt / za);
+			const double qv1 = qsv1 / (1.0 - qsv1);
+			const double rhom1 = DW(DW_RHOD, 0) / (1.0 - qsv1);
+			DW(DW_U, 0) = u1 / (1.0 + dt * Cd * wind / za);
+			DW(DW_V, 0) = v1 / (1.0 + dt * Cd * wind / za);
+			DW(DW_QSV, 0) = qsv1; DW(DW_T, 0) = t1; DW(DW_QV, 0) = qv1; DW(DW_RHOM, 0) = rhom1;
+			DW(DW_P, 0) = t1 * rhom1 * rair * (1.0 + zvir * qv1);
+		}
+		// ---- :379-419 boundary layer: theta, forward sweep (Thomas) ----
+		double km_k = 0.0, ke_k = 0.0;                         // Km(k), Ke(k) at the interface below level k
+		double em = 0.0, ee = 0.0, fu = 0.0, fv = 0.0, ft = 0.0, fq = 0.0;
+		double rhom_k = DW(DW_RHOM, 0), z_k = ZL(0), zi_k = ZI(0);
+		for (int k = 0; k < L; k++) {
+			const double pk_ = DW(DW_P, k);
+			const double th = DW(DW_T, k) * tmx_ref_pow(p0 / pk_, rdcp);
+			DW(DW_TH, k) = th;
+			double km_n = 0.0, ke_n = 0.0, rhom_n = 0.0, z_n = 0.0;
+			const double zi_n = ZI(k + 1);
+			if (k < L - 1) {
+				rhom_n = DW(DW_RHOM, k + 1); z_n = ZL(k + 1);
+				const double p_n = DW(DW_P, k + 1);
+				if (PBL == 0) {
+					const double presi = 0.5 * ((k == 0 ? p1_old : pk_) + p_n);
+					if (presi >= pbltop) {
+						km_n = Cd * wind * za;
+						ke_n = C * wind * za;
+					} else {
+						const double d = pbltop - presi;
+						const double ex = tmx_ref_exp(-(d * d) / (pblconst * pblconst));
+						km_n = Cd * wind * za * ex;
+						ke_n = C * wind * za * ex;
+					}
+				} else {
+					if (zi_n <= zpbltop) {
+						km_n = vkappa * sqrt(Cd) * wind * zi_n * (1.0 - zi_n / zpbltop) * (1.0 - zi_n / zpbltop);
+						ke_n = vkappa * sqrt(C) * wind * zi_n * (1.0 - zi_n / zpbltop) * (1.0 - zi_n / zpbltop);
+					}
+				}
+			}
+			double CA = 0.0, CC = 0.0;
+			if (k != 0) CA = 0.5 * (DW(DW_RHOM, k - 1) + rhom_k) / rhom_k * dt / (z_k - ZL(k - 1)) / (zi_n - zi_k);
+			if (k != L - 1) CC = 0.5 * (rhom_k + rhom_n) / rhom_k * dt / (z_n - z_k) / (zi_n - zi_k);
+			const double CAm = CA * km_k, CCm = CC * km_n, CAE = CA * ke_k, CCE = CC * ke_n;
+			const double CBm = 1.0 + CAm + CCm, CBE = 1.0 + CAE + CCE;
+			if (k == 0) {
+				em = CCm / CBm; ee = CCE / CBE;
+				fu = DW(DW_U, 0) / CBm; fv = DW(DW_V, 0) / CBm; ft = th / CBE; fq = DW(DW_QSV, 0) / CBE;
+			} else {
+				const double dm = CBm - CAm * em, de = CBE - CAE * ee;
+				em = CCm / dm; ee = CCE / de;
+				fu = (DW(DW_U, k) + CAm * fu) / dm;
+				fv = (DW(DW_V, k) + CAm * fv) / dm;
+				ft = (th + CAE * ft) / de;
+				fq = (DW(DW_QSV, k) + CAE * fq) / de;
+			}
+			DT(0, k) = em; DT(1, k) = ee; DT(2, k) = fu; DT(3, k) = fv; DT(4, k) = ft; DT(5, k) = fq;
+			km_k = km_n; ke_k = ke_n; rhom_k = rhom_n; z_k = z_n; zi_k = zi_n;
+		}
+		// ---- :421-432 back substitution; :434-442 back to qv, rhom, p ----
+		double u = fu, v = fv, th = ft, qsv = fq;
+		for (int k = L - 1; k >= 0; k--) {
+			if (k < L - 1) {
+				const double emk = DT(0, k), eek = DT(1, k);
+				u = emk * u + DT(2, k);
+				v = emk * v + DT(3, k);
+				th = eek * th + DT(4, k);
+				qsv = eek * qsv + DT(5, k);
+			}
+			const double qv = qsv / (1.0 - qsv);
+			const double rhom = DW(DW_RHOD, k) / (1.0 - qsv);
+			const double thetav = th * (1.0 + zvir * qv);
+			DW(DW_U, k) = u; DW(DW_V, k) = v; DW(DW_QV, k) = qv;
+			DW(DW_P, k) = p0 * tmx_ref_pow(rhom * rair * thetav / p0, cpcv);
+		}
+	}
+	prect[col] += precl * dt;                                           // DCMIPPhysics.cpp:299
+	// ---- DCMIPPhysics.cpp:326-387: back to the state ----
+	const double adiv = cf[DC_ADIV * NS + col], aa0 = cf[DC_AA0 * NS + col], aa1 = cf[DC_AA1 * NS + col], ab0 = cf[DC_AB0 * NS + col], ab1 = cf[DC_AB1 * NS + col];
+	for (int k = 0; k < L; k++) {
+		const double qv = DW(DW_QV, k), qc = DW(DW_QC, k), qr = DW(DW_QR, k), pr = DW(DW_P, k);
+		const double rho = DW(DW_RHOD, k) / (1.0 - qv - qc - qr);
+		const double tv = pr / (rho * p.Rd);
+		x[(size_t)TMX_SLAB_R(L, k) * NS + col] = rho;
+		x[(size_t)TMX_SLAB_T(L, k) * NS + col] = tv * tmx_ref_pow(p.p0 / pr, kappa) * rho;
+		x[(size_t)TMX_SLAB_Q(L, 0, k) * NS + col] = qv * rho;
+		x[(size_t)TMX_SLAB_Q(L, 1, k) * NS + col] = qc * rho;
+		x[(size_t)TMX_SLAB_Q(L, 2, k) * NS + col] = qr * rho;
+		const double lon = DW(DW_U, k) / adiv, lat = DW(DW_V, k);
+		x[(size_t)TMX_SLAB_U(L, k) * NS + col] = (aa0 * lon + aa1 * lat) * a;
+		x[(size_t)TMX_SLAB_V(L, k) * NS + col] = (ab0 * lon + ab1 * lat) * a;
+	}
+#undef DW
+#undef DT
+#undef ZL
+#undef ZI
+}
+
+size_t tmxk_dcmip_lds_bytes(int L) {
+	const size_t b = (size_t)6 * L * 64 * sizeof(double);
+	return b <= 160 * 1024 ? b : 0;
+}
+
+template <int PBL, int PREC>
+static void launch_dcmip(tmx_engine * e, const KParams & p, double * x, double dt, int test, double gamma, double pscal, double kappa, double a, bool lds) {
+	const dim3 grid((p.ncol + 63) / 64), blk(64);
+	if (lds) {
+		const size_t b = tmxk_dcmip_lds_bytes(p.L);
+		if (b > 48 * 1024) hipFuncSetAttribute((const void *)k_dcmip<PBL, PREC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+		hipLaunchKernelGGL((k_dcmip<PBL, PREC, true>), grid, blk, b, e->stream, p, x, (const double *)e->d_zlev, (const double *)e->d_zint,
+			(const double *)e->d_dcmip, e->d_dcw, e->d_prect, dt, test, gamma, pscal, kappa, a);
+	} else {
+		hipLaunchKernelGGL((k_dcmip<PBL, PREC, false>), grid, blk, 0, e->stream, p, x, (const double *)e->d_zlev, (const double *)e->d_zint,
+			(const double *)e->d_dcmip, e->d_dcw, e->d_prect, dt, test, gamma, pscal, kappa, a);
+	}
+}
+
+void tmxk_dcmip(tmx_engine * e, const KParams & p, double * x, double dt, int test, int pbl, int prec, double earth_radius, bool lds) {
+	// PhysicalConstants::GetGamma / GetKappa / pressure scaling (src/atm/PhysicalConstants.h:355-384), host libm as in the reference
+	const double gamma = p.cp / (p.cp - p.Rd), kappa = p.Rd / p.cp;
+	const double pscal = p.p0 * pow(p.Rd / p.p0, gamma);
+	if (pbl == 0 && prec == 0) launch_dcmip<0, 0>(e, p, x, dt, test, gamma, pscal, kappa, earth_radius, lds);
+	else if (pbl == 0) launch_dcmip<0, 1>(e, p, x, dt, test, gamma, pscal, kappa, earth_radius, lds);
+	else if (prec == 0) launch_dcmip<1, 0>(e, p, x, dt, test, gamma, pscal, kappa, earth_radius, lds);
+	else launch_dcmip<1, 1>(e, p, x, dt, test, gamma, pscal, kappa, earth_radius, lds);
+}
+
 // gather the copies other ranks need into the send buffer, one contiguous message per peer:
 // sendbuf = [peer][slab][count_peer]; entry i of the plan lives at base[i] + slab * stride[i]

@@ -2055,6 +2055,23 @@ extern "C" int tmx_set_patch_level_heights(tmx_engine * e, int patch, const doub
 	return TMX_OK;
 }
 
+// level heights and the precipitation accumulator of the column physics (Kessler, DCMIP2016), allocated at first use; uploads changed heights
+int column_physics_levels(tmx_engine * e) {
+	const size_t NS = e->NS; const int L = e->L;
+	if (!e->d_zlev) {
+		HIPCHK(hipMalloc((void **)&e->d_zlev, (size_t)L * NS * sizeof(double)));
+		HIPCHK(hipMalloc((void **)&e->d_prect, NS * sizeof(double)));
+		HIPCHK(hipMemset(e->d_prect, 0, NS * sizeof(double)));
+		e->hbm_bytes += (size_t)(L + 1) * NS * sizeof(double);
+	}
+	if (e->zlev_dirty) {
+		HIPCHK(hipStreamSynchronize(e->stream));
+		HIPCHK(hipMemcpy(e->d_zlev, e->h_zlev.data(), (size_t)L * NS * sizeof(double), hipMemcpyHostToDevice));
+		e->zlev_dirty = false;
+	}
+	return TMX_OK;
+}
+
 extern "C" int tmx_physics_kessler(tmx_engine * e, int instance, double dt) {
 	int r; if ((r = check_ready(e)) || (r = check_inst(e, instance))) return r;
 	REQUIRE(!e->sw, TMX_ERR_UNSUPPORTED, "Kessler physics with the shallow-water equation set is not supported");
@@ -2063,17 +2080,10 @@ extern "C" int tmx_physics_kessler(tmx_engine * e, int instance, double dt) {
 	for (int lp : e->local_patches)
 		REQUIRE(e->patches[lp].zlev_set, TMX_ERR_INVALID, "tmx_set_patch_level_heights was not called for patch %d", lp);
 	const size_t NS = e->NS; const int L = e->L;
-	if (!e->d_zlev) {
-		HIPCHK(hipMalloc((void **)&e->d_zlev, (size_t)L * NS * sizeof(double)));
-		HIPCHK(hipMalloc((void **)&e->d_prect, NS * sizeof(double)));
-		HIPCHK(hipMemset(e->d_prect, 0, NS * sizeof(double)));
+	if ((r = column_physics_levels(e))) return r;
+	if (!e->d_kes) {
 		HIPCHK(hipMalloc((void **)&e->d_kes, (size_t)8 * L * NS * sizeof(double)));
-		e->hbm_bytes += (size_t)(9 * L + 1) * NS * sizeof(double);
-	}
-	if (e->zlev_dirty) {
-		HIPCHK(hipStreamSynchronize(e->stream));
-		HIPCHK(hipMemcpy(e->d_zlev, e->h_zlev.data(), (size_t)L * NS * sizeof(double), hipMemcpyHostToDevice));
-		e->zlev_dirty = false;
+		e->hbm_bytes += (size_t)8 * L * NS * sizeof(double);
 	}
 	ProfScope ps(e, TMX_K_LINCOMB);
 	tmxk_kessler(e, make_params(e), inst(e, instance), dt);

@@ -129,6 +129,10 @@ def load_library(flavour=None):
     lib.tmx_set_patch_element_spacing.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
     lib.tmx_physics_kessler.argtypes = [C.c_void_p, C.c_int, C.c_double]
     lib.tmx_download_precipitation.argtypes = [C.c_void_p, C.c_int, PD, C.c_int]
+    lib.tmx_set_patch_dcmip_inputs.argtypes = [C.c_void_p, C.c_int, PD, PD, PD, PD, C.c_double]
+    lib.tmx_physics_dcmip2016.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]
+    lib.tmx_debug_dcmip_node_coefficients.argtypes = [C.c_int, C.c_double, C.c_double, PD]
+    lib.tmx_debug_dcmip_tsurf.argtypes = [C.c_double, PD]
     lib.tmx_upload_tracers.argtypes = [C.c_void_p, C.c_int, C.c_int, PD]
     lib.tmx_download_tracers.argtypes = [C.c_void_p, C.c_int, C.c_int, PD]
     lib.tmx_comm_init.argtypes = [C.c_void_p, C.c_char_p]
@@ -358,6 +362,23 @@ class Engine:
     def kessler(self, instance, dt):
         """KesslerPhysics::Perform (test/dcmip2016/KesslerPhysics.cpp:83-285 + interface/kessler.f90)."""
         self._chk(self.lib.tmx_physics_kessler(self.h, instance, dt))
+
+    def set_dcmip_inputs(self, latitude=None, a_nodes=None, b_nodes=None, z_interfaces=None, earth_radius=None):
+        """Column inputs of DCMIPPhysics::Perform per patch: ``latitude[p] = [na][nb]`` (GetLatitude), ``a_nodes[p] = [na]`` /
+        ``b_nodes[p] = [nb]`` (GetANode / GetBNode), ``z_interfaces[p] = [na][nb][L+1]`` (GetZInterfaces); defaults: the grid's
+        own, and the grid's earth radius.  The level heights come through set_level_heights."""
+        a = self.grid.phys.earth_radius if earth_radius is None else earth_radius
+        for p in self.local_patches:
+            P = self.grid.patches[p]
+            la = np.ascontiguousarray(P.lat if latitude is None else latitude[p], dtype=np.float64)
+            an = np.ascontiguousarray(P.a_nodes if a_nodes is None else a_nodes[p], dtype=np.float64)
+            bn = np.ascontiguousarray(P.b_nodes if b_nodes is None else b_nodes[p], dtype=np.float64)
+            zi = np.ascontiguousarray(P.geom["z_interfaces"] if z_interfaces is None else z_interfaces[p], dtype=np.float64)
+            self._chk(self.lib.tmx_set_patch_dcmip_inputs(self.h, p, _pd(la), _pd(an), _pd(bn), _pd(zi), float(a)))
+
+    def dcmip2016(self, instance, dt, test, pbl_type, prec_type):
+        """DCMIPPhysics::Perform (test/dcmip2016/DCMIPPhysics.cpp:156-409 + interface/dcmip_physics_z_v1.f90)."""
+        self._chk(self.lib.tmx_physics_dcmip2016(self.h, instance, dt, test, pbl_type, prec_type))
 
     def download_precipitation(self, reset=False):
         out = {}
