@@ -2,11 +2,16 @@
 """Benchmark of the hot path on MI355X: whole ARS343 IMEX steps of the Jablonowski-Williamson
 baroclinic wave on the cubed sphere (BASELINE.json metric: element-DOF-updates/s and SYPD).
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]        (N>1: launched by torch.distributed.run)
 
 A "step" is one full TimestepSchemeARS343::Step (4 H-explicit, 4 V-explicit, 3 V-implicit column
 solves, 6 DSS incl. exchange, stage algebra, two-pass hyperviscosity) on synthetic input of the
 reference's own closed-form initial state, resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line with the headline
+(`value`, `ms_per_step`, `sypd`) and the configuration.  `--full` adds everything else below, each in runs of its
+own after the timed steps: the HIP-event profile pass behind `roofline` and `kernel_ms_per_step`, the sustained leg,
+the finiteness check, the N > 1 parity leg and per-rank kernel split, and the CPU baselines.
 
   value       element-DOF-updates/s = N_el * 16 * L * 5 * K / wall      (whole job, all ranks)
   roofline    dominant operation: algorithmic bytes / measured device time (HIP events)
@@ -346,6 +351,42 @@ def projected_from_rank_share(world, ne, L, measured_ms):
         return None
 
 
+def initial_state(grid, test):
+    """grid.evaluate_test_case(test), the input of every step, with its hot spot spread over host threads.  Nearly all of the
+    serial evaluation's time (~20 s at ne30 L30) is test.eta_from_z, the vectorised Newton solve for eta at every node, called
+    for the levels and for the interfaces of each patch, once for the state and once for the reference state.  It is first run
+    for those inputs on a thread pool (numpy releases the GIL inside its array operations); the evaluation then takes each
+    call's result by the exact bytes of its input, so it receives the arrays the serial evaluation computes.  A call whose
+    input was not foreseen computes as before."""
+    import hashlib
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+
+    def key(z, lat):
+        return z.shape, z.dtype.str, hashlib.sha1(np.ascontiguousarray(z)).digest(), hashlib.sha1(np.ascontiguousarray(lat)).digest()
+
+    # the heights evaluate_test_case will pass (it repeats these calls; their results do not change)
+    test.evaluate_physical_constants(grid.phys)
+    grid.set_topography(test.evaluate_topography)
+    grid.evaluate_geometric_terms()
+    solve = test.eta_from_z
+    with ThreadPoolExecutor(min(16, len(os.sched_getaffinity(0)))) as pool:
+        pending = {}
+        for P in grid.patches:
+            for z in (P.geom["z_levels"], P.geom["z_interfaces"]):
+                lat = P.lat[..., None] * np.ones(z.shape[-1])
+                pending.setdefault(key(z, lat), pool.submit(solve, grid.phys, z, lat))
+
+        def prefetched(phys, z, lat):
+            f = pending.get(key(z, lat)) if phys is grid.phys else None
+            return f.result() if f is not None else solve(phys, z, lat)
+        test.eta_from_z = prefetched
+        try:
+            return grid.evaluate_test_case(test)
+        finally:
+            del test.eta_from_z
+
+
 DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: size limit of the .npy files together
 
 
@@ -395,7 +436,10 @@ def main():
     ap.add_argument("--levels", type=int, default=30)
     ap.add_argument("--dt", type=float, default=150.0)
     ap.add_argument("--ppd", type=int, default=2, help="patches per panel direction (2 -> 24 patches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the profile pass (roofline, kernel_ms_per_step), the sustained leg, the finiteness "
+                         "check, the N > 1 parity leg and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--develop", type=int, default=10, help="untimed steps before the warm-up (developed state)")
     ap.add_argument("--halo", default=os.environ.get("TMX_HALO", "rccl"), choices=["auto", "rccl", "p2p"],
                     help="multi-rank halo transport: rccl (default) = RCCL send/recv; p2p = peer-to-peer writes into IPC-mapped ghost buffers; "
@@ -408,9 +452,9 @@ def main():
                     help="strong (default, the headline): the ne30 problem is fixed as --gpus grows.  weak: the grid grows with the rank count, "
                          "ne = the multiple of 2 nearest to --ne * sqrt(gpus) (30 / 42 / 60 / 84 at 1 / 2 / 4 / 8), dt scaled with the element width")
     ap.add_argument("--sustained-steps", type=int, default=2000,
-                    help="steps of the untimed sustained leg after the timed region (clock / power before and after are reported; 0: skip)")
+                    help="--full: steps of the untimed sustained leg after the timed region (clock / power before and after are reported; 0: skip)")
     ap.add_argument("--parity-steps", type=int, default=3,
-                    help="N > 1: after the timing, all ranks and a single-rank engine on rank 0 step this many times from the initial state and "
+                    help="--full, N > 1: after the timing, all ranks and a single-rank engine on rank 0 step this many times from the initial state and "
                          "rank 0's patches are compared bit for bit (0: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the state they produced as DIR/<name>.npy (float64, at most 64 MB: a fixed sample of "
@@ -457,7 +501,7 @@ def main():
         ne = 2 * int(round(args.ne * (world ** 0.5) / 2.0))
         dt = args.dt * args.ne / ne
     grid = CubedSphereGrid(ne, L, 30000.0, ppd=args.ppd)
-    states = grid.evaluate_test_case(BaroclinicWaveJW(0.0, 30000.0, "exp"))
+    states = initial_state(grid, BaroclinicWaveJW(0.0, 30000.0, "exp"))
     eng = Engine(grid, rank=rank, n_ranks=world, device=local_rank)
     halo_note = "RCCL send/recv"
     if world > 1:
@@ -583,87 +627,89 @@ def main():
         eng.step_ars343(dt)
     barrier()
     wall = time.perf_counter() - t0
-    unique_after_timed = eng.info(13)      # data instances in node-unique form when the timed region ended
-    if args.dump_outputs:
-        written, ncol = dump_outputs(eng, grid, args.dump_outputs)
-        sys.stderr.write("bench: state after the %d timed steps written to %s (%d of %d columns)\n" % (args.steps, args.dump_outputs, written, ncol))
-    # per-kernel device time: the same K steps again with HIP events around every launch on the
-    # engine's stream (kept out of the timed region: the event markers cost a few % of wall time)
-    eng.profile_enable(True)
-    eng.profile_reset()
-    eng.pivot_stats(True)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.step_ars343(dt)
-    barrier()
-    wall_prof = time.perf_counter() - t1
-    prof = eng.profile()
-    pivot = eng.pivot_stats(False)
-    eng.profile_enable(False)
+    wall = time.perf_counter() - t0
     if world > 1:
         tt = torch.tensor([wall], dtype=torch.float64, device="cpu" if args.share_device else "cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
-
-    # sustained leg (untimed for `value`): enough steps for clocks and power to settle, with the SMI readings on both sides
-    sustained = None
-    if args.sustained_steps > 0:
-        smi0 = smi_snapshot() if rank == 0 else None
-        barrier()
-        ts0 = time.perf_counter()
-        for _ in range(args.sustained_steps):
+    unique_after_timed = eng.info(13)      # data instances in node-unique form when the timed region ended
+    if args.dump_outputs:
+        written, ncol = dump_outputs(eng, grid, args.dump_outputs)
+        sys.stderr.write("bench: state after the %d timed steps written to %s (%d of %d columns)\n" % (args.steps, args.dump_outputs, written, ncol))
+    ablation_build = bool(os.environ.get("TMX_LIBRARY"))      # tools/ablate.sh builds skip parts of the arithmetic on purpose
+    if args.full:
+        # per-kernel device time: the same K steps again with HIP events around every launch on the
+        # engine's stream (kept out of the timed region: the event markers cost a few % of wall time)
+        eng.profile_enable(True)
+        eng.profile_reset()
+        eng.pivot_stats(True)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
             eng.step_ars343(dt)
         barrier()
-        ts = time.perf_counter() - ts0
-        if world > 1:
-            tt = torch.tensor([ts], dtype=torch.float64, device="cpu" if args.share_device else "cuda")
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            ts = float(tt.item())
-        sustained = {"steps": args.sustained_steps, "seconds": ts, "ms_per_step": 1e3 * ts / args.sustained_steps,
-                     "smi_before": smi0, "smi_after": smi_snapshot() if rank == 0 else None}
+        wall_prof = time.perf_counter() - t1
+        prof = eng.profile()
+        pivot = eng.pivot_stats(False)
+        eng.profile_enable(False)
 
-    # sanity: the state the timed and sustained legs produced must still be finite (checked BEFORE the parity leg re-uploads the initial state)
-    import numpy as np
-    chk = eng.download_state(0)
-    state_finite = all(np.isfinite(chk[p][0]).all() and np.isfinite(chk[p][1][3]).all() for p in eng.local_patches)
-    del chk
+        # sustained leg (untimed for `value`): enough steps for clocks and power to settle, with the SMI readings on both sides
+        sustained = None
+        if args.sustained_steps > 0:
+            smi0 = smi_snapshot() if rank == 0 else None
+            barrier()
+            ts0 = time.perf_counter()
+            for _ in range(args.sustained_steps):
+                eng.step_ars343(dt)
+            barrier()
+            ts = time.perf_counter() - ts0
+            if world > 1:
+                tt = torch.tensor([ts], dtype=torch.float64, device="cpu" if args.share_device else "cuda")
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                ts = float(tt.item())
+            sustained = {"steps": args.sustained_steps, "seconds": ts, "ms_per_step": 1e3 * ts / args.sustained_steps,
+                         "smi_before": smi0, "smi_after": smi_snapshot() if rank == 0 else None}
 
-    # N > 1: the line carries its own parity proof -- every rank steps again from the initial state, rank 0 also steps a
-    # single-rank engine holding all patches, and rank 0's patches must come out identical, bit for bit
-    parity = None
-    if world > 1 and args.parity_steps > 0 and not hs:
-        eng.upload_state(0, states)
-        for _ in range(args.parity_steps):
-            _step(dt)
-        barrier()
-        got = eng.download_state(0)
-        if rank == 0:
-            one = Engine(grid, rank=0, n_ranks=1, device=local_rank)
-            one.upload_state(0, states)
-            for _ in range(args.parity_steps):
-                one.step_ars343(dt)
-            one.sync()
-            ref = one.download_state(0)
-            same = all(np.array_equal(got[p][0], ref[p][0]) and np.array_equal(got[p][1], ref[p][1]) for p in eng.local_patches)
-            worst = max(float(np.max(np.abs(got[p][0] - ref[p][0]))) for p in eng.local_patches)
-            parity = {"steps": args.parity_steps, "patches_compared": len(eng.local_patches), "identical_to_single_rank_engine": bool(same),
-                      "max_abs_difference": worst}
-            one.close()
-        barrier()
-
-    if parity is not None or (world > 1 and args.parity_steps > 0 and not hs):      # ... and the state behind the parity leg as well
+        # sanity: the state the timed and sustained legs produced must still be finite (checked BEFORE the parity leg re-uploads the initial state)
+        import numpy as np
         chk = eng.download_state(0)
-        state_finite = state_finite and all(np.isfinite(chk[p][0]).all() and np.isfinite(chk[p][1][3]).all() for p in eng.local_patches)
-    ablation_build = bool(os.environ.get("TMX_LIBRARY"))      # tools/ablate.sh builds skip parts of the arithmetic on purpose
-    if not state_finite and not ablation_build:
-        sys.exit("bench.py: state became non-finite")
+        state_finite = all(np.isfinite(chk[p][0]).all() and np.isfinite(chk[p][1][3]).all() for p in eng.local_patches)
+        del chk
 
-    # N > 1: every rank's kernel split travels to rank 0 (the first multi-GPU record should explain itself)
-    rank_kernels = None
-    if world > 1:
-        mine = {k: v[0] / args.steps for k, v in prof.items()}
-        rank_kernels = [None] * world
-        dist.all_gather_object(rank_kernels, mine)
+        # N > 1: the line carries its own parity proof -- every rank steps again from the initial state, rank 0 also steps a
+        # single-rank engine holding all patches, and rank 0's patches must come out identical, bit for bit
+        parity = None
+        if world > 1 and args.parity_steps > 0 and not hs:
+            eng.upload_state(0, states)
+            for _ in range(args.parity_steps):
+                _step(dt)
+            barrier()
+            got = eng.download_state(0)
+            if rank == 0:
+                one = Engine(grid, rank=0, n_ranks=1, device=local_rank)
+                one.upload_state(0, states)
+                for _ in range(args.parity_steps):
+                    one.step_ars343(dt)
+                one.sync()
+                ref = one.download_state(0)
+                same = all(np.array_equal(got[p][0], ref[p][0]) and np.array_equal(got[p][1], ref[p][1]) for p in eng.local_patches)
+                worst = max(float(np.max(np.abs(got[p][0] - ref[p][0]))) for p in eng.local_patches)
+                parity = {"steps": args.parity_steps, "patches_compared": len(eng.local_patches), "identical_to_single_rank_engine": bool(same),
+                          "max_abs_difference": worst}
+                one.close()
+            barrier()
+
+        if parity is not None or (world > 1 and args.parity_steps > 0 and not hs):      # ... and the state behind the parity leg as well
+            chk = eng.download_state(0)
+            state_finite = state_finite and all(np.isfinite(chk[p][0]).all() and np.isfinite(chk[p][1][3]).all() for p in eng.local_patches)
+        if not state_finite and not ablation_build:
+            sys.exit("bench.py: state became non-finite")
+
+        # N > 1: every rank's kernel split travels to rank 0 (the first multi-GPU record should explain itself)
+        rank_kernels = None
+        if world > 1:
+            mine = {k: v[0] / args.steps for k, v in prof.items()}
+            rank_kernels = [None] * world
+            dist.all_gather_object(rank_kernels, mine)
 
     if rank == 0:
         n_el = 6 * ne * ne
@@ -671,66 +717,6 @@ def main():
         points = 6 * (ne * 4) ** 2 * L
         ms_per_step = 1e3 * wall / args.steps
         value = dof_per_step * args.steps / wall
-        # dominant operation of the step on this rank; a launch = one call of the operation (its kernels together)
-        op_time = {op: sum(prof[k][0] for k in ks) for op, ks in OP_KERNELS.items()}
-        # The roofline object is for the dominant KERNEL as `rocprofv3 --stats` ranks them.  The HIP events of this run time whole
-        # operations (the explicit stage = several instantiations of k_h_explicit + k_h_w_update), so the kernel ranking is read
-        # from the committed kernel-trace profile of this workload shape; without one the top operation is taken unscaled.
-        dk = dominant_kernel_from_stats(ne, L, world)
-        if dk is not None:
-            dom, dom_note = dk[0], "dominant kernel per %s: %s (%.1f %% of kernel time there)" % (dk[3], dk[1], 100.0 * dk[2])
-        else:
-            dom = max((op for op in op_time if ALG_BYTES[op] > 0), key=lambda op: op_time[op])
-            dom_note = "no committed kernel-trace profile of this shape: the operation with the largest summed time of this run (several kernels)"
-        op_launches = {op: max(sum(prof[k][1] for k in ks), 1) for op, ks in OP_KERNELS.items()}
-        avg_ms = op_time[dom] / op_launches[dom]
-        local_points = points / world
-        # headline `achieved` / `frac`: SURVEY 8(d)'s row x the points the kernel really PROCESSES -- unique (node, level) points where the
-        # node-unique layout ran or the operation is the column solve, stored points otherwise; the same row on the stored points (rounds
-        # 1-5's headline) stays beside it as frac_8d_row_on_stored_points
-        proc_points = (eng.info(1) * L) if (eng.info(12) == 1 and unique_after_timed > 0) or dom == "v_implicit" else local_points
-        achieved = ALG_BYTES[dom] * proc_points / (avg_ms * 1e-3) / 1e9
-        achieved_stored = ALG_BYTES[dom] * local_points / (avg_ms * 1e-3) / 1e9
-        op_share = {op: op_time[op] / max(sum(op_time.values()), 1e-12) for op in op_time}
-        dom_op = max(op_share, key=lambda op: op_share[op])
-        walk = eng.get_option("h_walk") != 0 and eng.info(12) == 1 and unique_after_timed > 0
-        kernel_name = {"h_explicit": "k_h_walk<NT> (column-segment walk)" if walk else "k_h_explicit<true,NT>+k_h_w_update<NT>", "v_implicit": "k_vi_pair (two wavefronts per column group)",
-                       "dss": "k_dss", "hypervis": "k_hypervis", "lincomb": "k_lincomb"}[dom]
-        if dom == "v_implicit" and eng.info(20) == 2:      # TMX_INFO_COLUMN_KERNEL: the kernel that really ran
-            kernel_name = "k_vi_group (one column per 16-lane group)"
-        mfma = mfma_report(eng.get_option("contraction_mfma") != 0)
-        # second accounting, for the layout that ran (layout_model above) and the measured HBM rate = counter traffic / this run's time
-        unique_ran = eng.info(12) == 1 and unique_after_timed > 0
-        lay = layout_model(eng, L, unique_ran)
-        lay_dom = lay[dom]
-        dom_traffic = measured_traffic(dom, ne, L, world, op_launches[dom] / args.steps)
-        tpath, ttab = traffic_table(ne, L, world)
-        step_traffic = None
-        if ttab is not None:
-            known = {n for names in OP_ROCPROF.values() for n in names}
-            step_traffic = sum(r["hbm_bytes_per_launch"] * r["launches"] / ttab["steps"] for k, r in ttab["kernels"].items()
-                               if kernel_base(k) in known)
-        sha_now = csrc_sha16()
-        sha_prof = (ttab or {}).get("csrc_sha16")
-
-        def per_op(op):
-            # algorithmic figure (SURVEY 8d row x points) beside the counter-measured one: the 8d rows are not lower bounds for
-            # fused passes (hypervis reads less than its row says), so "measured_GBs" is the rate to judge those by
-            ms = op_time[op] / op_launches[op]
-            tr = measured_traffic(op, ne, L, world, op_launches[op] / args.steps)
-            extra = {}
-            if op == "v_implicit":
-                # what the column solve cannot avoid moving as designed (unique columns read once, the three solved variables
-                # written to every stored column): the SURVEY row above also counts 26 metric doubles this kernel no longer
-                # reads, and the measured traffic is mostly the U-row stream of the band LU going to HBM and back
-                extra["compulsory_bytes_per_launch"] = 8.0 * ((5 * L + 1) * eng.info(1) + (3 * L + 1) * eng.info(0))
-            return {"launches_per_step": op_launches[op] / args.steps, "ms_per_launch": ms, **extra,
-                    "achieved_GBs": ALG_BYTES[op] * local_points / max(ms * 1e-3, 1e-12) / 1e9,
-                    "bytes_per_point": ALG_BYTES[op], "survey_8d_bytes_per_point": SURVEY_8D_BYTES[op],
-                    "achieved_GBs_with_survey_8d_row": SURVEY_8D_BYTES[op] * local_points / max(ms * 1e-3, 1e-12) / 1e9,
-                    "traffic": tr, "measured_GBs": (tr / max(ms * 1e-3, 1e-12) / 1e9) if tr else None,
-                    "layout_aware_bytes_per_launch": lay[op], "layout_aware_GBs": lay[op] / max(ms * 1e-3, 1e-12) / 1e9,
-                    "bound": OP_BOUND[op]}
         out = {
             "metric": "element-DOF-updates/s (JW baroclinic wave ne%d np4 L%d, ARS343 IMEX)" % (ne, L),
             "value": value, "unit": "element-DOF-updates/s",
@@ -745,58 +731,12 @@ def main():
                            len(grid.patches), world, "processes sharing ONE GPU (multi-process path check, not a scaling number)" if args.share_device and world > 1 else "GPU(s)",
                            halo_note),
                        "hbm_allocated_GiB_per_gpu": eng.info(5) / 2.0 ** 30,
-                       # the sustained leg beside the K timed steps (full record: top-level "sustained")
-                       "sustained_steps": sustained["steps"] if sustained else 0,
-                       "sustained_ms_per_step": sustained["ms_per_step"] if sustained else None,
-                       "sustained_value": (dof_per_step / (sustained["ms_per_step"] * 1e-3)) if sustained else None,
                        # tmx_set_option("unique_layout") / TMX_UNIQUE: inside tmx_step the state is held once per patch node
                        "state_layout": ("node-unique inside tmx_step (%d instances in that form at the end of the timed region, %d partial slots, "
                                         "%d node groups left to the DSS kernel of %d)" % (unique_after_timed, eng.info(15), eng.info(16), eng.info(2)))
                                        if eng.info(12) == 1 else "element-major (16 nodes per element, seam nodes duplicated)"},
-            # `bound`: the roofline `frac` is priced against (HBM: every kernel of the path is fp64 stencil / band work, no GEMM); `limiter`: what
-            # limits the dominant operation as measured ("hbm", or "latency" for the column solve: dependent fp64 chains of its two co-scheduled
-            # wavefronts beside the U-row stream, see `limited_by`)
-            "roofline": {"bound": "hbm", "limiter": "hbm" if OP_BOUND[dom].startswith("hbm") else "latency", "priced_against": "hbm",
-                         "kernel": kernel_name, "operation": dom, "dominant_by": dom_note,
-                         "dominant_operation": dom_op, "operation_share_of_kernel_time": {op: round(v, 4) for op, v in op_share.items()},
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "points_processed_per_launch": proc_points, "points_stored": local_points,
-                         "achieved_8d_row_on_stored_points": achieved_stored, "frac_8d_row_on_stored_points": achieved_stored / HBM_PEAK_GBS,
-                         "traffic": dom_traffic, "avg_launch_ms": avg_ms,
-                         "algorithmic_bytes_per_launch": ALG_BYTES[dom] * proc_points,
-                         # (1) the same 8(d) row on the points this layout holds (the column solve works on the unique columns, not the stored ones)
-                         "achieved_8d_row_on_layout_points": (ALG_BYTES[dom] * (eng.info(1) if (unique_ran or dom == "v_implicit") else eng.info(0)) * L) / (avg_ms * 1e-3) / 1e9,
-                         "frac_8d_row_on_layout_points": (ALG_BYTES[dom] * (eng.info(1) if (unique_ran or dom == "v_implicit") else eng.info(0)) * L) / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         # (2) layout-aware algorithmic bytes: what the operation cannot avoid moving in the layout that runs (layout_model)
-                         "layout_aware_bytes_per_launch": lay_dom, "achieved_layout_aware": lay_dom / (avg_ms * 1e-3) / 1e9,
-                         "frac_layout_aware": lay_dom / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         # (3) the HBM rate itself: counter traffic of the committed PMC table / this run's launch time
-                         "hbm_rate_GBs": (dom_traffic / (avg_ms * 1e-3) / 1e9) if dom_traffic else None,
-                         "hbm_rate_frac": (dom_traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if dom_traffic else None,
-                         "traffic_over_layout_aware_bytes": (dom_traffic / lay_dom) if (dom_traffic and lay_dom) else None,
-                         "whole_step_traffic_bytes": step_traffic,
-                         "whole_step_hbm_rate_GBs": (step_traffic / (ms_per_step * 1e-3) / 1e9) if step_traffic else None,
-                         "whole_step_hbm_rate_frac": (step_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS) if step_traffic else None,
-                         "whole_step_layout_aware_GBs": sum(lay[op] * op_launches[op] / args.steps for op in lay) / (ms_per_step * 1e-3) / 1e9,
-                         "traffic_source": os.path.relpath(tpath, ROOT) if tpath else None,
-                         "traffic_source_csrc_sha16": sha_prof, "library_csrc_sha16": sha_now,
-                         "traffic_source_matches_library_sources": (sha_prof == sha_now) if sha_prof else None,
-                         "per_operation": {op: per_op(op) for op in OP_KERNELS},
-                         "limited_by": OP_BOUND[dom],
-                         "uniform_pivot_fraction": (pivot[0] / pivot[1]) if pivot[1] else None,
-                         "whole_step_algorithmic_GBs": ALG_BYTES_PER_STEP * points * args.steps / wall / 1e9,
-                         # default path: no MFMA instruction is issued (the bit-exact contractions are LDS + VALU); with TMX_MFMA=1
-                         # the fused explicit kernel issues 12 v_mfma_f64_4x4x4_4b per point: counters in profiles/r02_mfma_ab.json
-                         "mfma_utilisation": mfma["active"], "mfma_ab": mfma["ab"],
-                         "offline_sources": "traffic, mfma_utilisation and mfma_ab are read from the committed rocprofv3 passes "
-                                            "(profiles/%s_*), not measured by this run; times and rates are this run's" % PROFILE_TAG,
-                         },
-            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in prof.items()},
-            "ms_per_step_with_event_markers": 1e3 * wall_prof / args.steps,
             "developed_steps": args.develop, "host_cpu_count": os.cpu_count(),
             "physics_after_every_step": args.physics,
-            "state_finite": bool(state_finite),
-            "sustained": sustained,
             # every engine option as this run used it (the library reads no environment variable on its own; what this script's
             # plumbing took from TMX_* variables is listed under from_environment)
             "engine_options": eng.options_report(),
@@ -810,27 +750,138 @@ def main():
             out["multi_rank"] = {"rccl_comm_ranks": eng.info(9), "halo_transport": {0: "none", 1: "rccl", 2: "p2p", 3: "loopback"}.get(eng.info(11), "?"),
                                  "rank0_message_bytes_per_peer": {str(k): v * nslab * 8 for k, v in sorted(per_peer.items())},
                                  "rank0_early_tiles": eng.info(7), "rank0_late_tiles": eng.info(8),
-                                 "parity": parity,
-                                 "per_rank_kernel_ms_per_step": rank_kernels,
-                                 "projected_from_rank_share": projected_from_rank_share(world, ne, L, ms_per_step),
                                  "scaling_note": "strong scaling of a ~1.2 ms step is Amdahl-limited: the per-rank compute share measured on one GPU (wire left out) "
                                                  "bounds the speed-up before any message is sent; weak scaling (--scaling weak: the grid grows with the rank count) is "
                                                  "the regime the design is for (11.2-12.8 G element-DOF-updates/s per GPU from ne30 to ne84, profiles/r06_other_shapes.txt)"}
         if ablation_build:      # a library named by TMX_LIBRARY: never a result, say so in the line itself
             out["ablation_build"] = True
             out["library"] = os.environ["TMX_LIBRARY"]
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(ne, L, dt, 6, 6)      # ~15 s of CPU work (1 warm-up + 6 timed steps)
-            mpi = cpu_baseline_mpi(ne, L, dt, 6)                     # + the reference's own 6-rank MPI run, ~20 core-seconds
-            if mpi is not None:
-                out["cpu_baseline_mpi"] = mpi
-            allc = cpu_baseline_allcores(ne, L, dt, 4)              # + 24 ranks on the 24-patch layout where the host has them
-            if allc is not None:
-                out["cpu_baseline_allcores"] = allc
-                # the fairest host figure travels INSIDE the cpu_baseline object as well (its headline fields stay the one-core run)
-                out["cpu_baseline"]["all_cores"] = {k: allc[k] for k in ("value", "unit", "cores", "kind", "sample") if k in allc}
-            if mpi is not None:
-                out["cpu_baseline"]["mpi_6_ranks"] = {k: mpi[k] for k in ("value", "unit", "cores", "kind", "sample") if k in mpi}
+        if args.full:
+            # dominant operation of the step on this rank; a launch = one call of the operation (its kernels together)
+            op_time = {op: sum(prof[k][0] for k in ks) for op, ks in OP_KERNELS.items()}
+            # The roofline object is for the dominant KERNEL as `rocprofv3 --stats` ranks them.  The HIP events of this run time whole
+            # operations (the explicit stage = several instantiations of k_h_explicit + k_h_w_update), so the kernel ranking is read
+            # from the committed kernel-trace profile of this workload shape; without one the top operation is taken unscaled.
+            dk = dominant_kernel_from_stats(ne, L, world)
+            if dk is not None:
+                dom, dom_note = dk[0], "dominant kernel per %s: %s (%.1f %% of kernel time there)" % (dk[3], dk[1], 100.0 * dk[2])
+            else:
+                dom = max((op for op in op_time if ALG_BYTES[op] > 0), key=lambda op: op_time[op])
+                dom_note = "no committed kernel-trace profile of this shape: the operation with the largest summed time of this run (several kernels)"
+            op_launches = {op: max(sum(prof[k][1] for k in ks), 1) for op, ks in OP_KERNELS.items()}
+            avg_ms = op_time[dom] / op_launches[dom]
+            local_points = points / world
+            # headline `achieved` / `frac`: SURVEY 8(d)'s row x the points the kernel really PROCESSES -- unique (node, level) points where the
+            # node-unique layout ran or the operation is the column solve, stored points otherwise; the same row on the stored points (rounds
+            # 1-5's headline) stays beside it as frac_8d_row_on_stored_points
+            proc_points = (eng.info(1) * L) if (eng.info(12) == 1 and unique_after_timed > 0) or dom == "v_implicit" else local_points
+            achieved = ALG_BYTES[dom] * proc_points / (avg_ms * 1e-3) / 1e9
+            achieved_stored = ALG_BYTES[dom] * local_points / (avg_ms * 1e-3) / 1e9
+            op_share = {op: op_time[op] / max(sum(op_time.values()), 1e-12) for op in op_time}
+            dom_op = max(op_share, key=lambda op: op_share[op])
+            walk = eng.get_option("h_walk") != 0 and eng.info(12) == 1 and unique_after_timed > 0
+            kernel_name = {"h_explicit": "k_h_walk<NT> (column-segment walk)" if walk else "k_h_explicit<true,NT>+k_h_w_update<NT>", "v_implicit": "k_vi_pair (two wavefronts per column group)",
+                           "dss": "k_dss", "hypervis": "k_hypervis", "lincomb": "k_lincomb"}[dom]
+            if dom == "v_implicit" and eng.info(20) == 2:      # TMX_INFO_COLUMN_KERNEL: the kernel that really ran
+                kernel_name = "k_vi_group (one column per 16-lane group)"
+            mfma = mfma_report(eng.get_option("contraction_mfma") != 0)
+            # second accounting, for the layout that ran (layout_model above) and the measured HBM rate = counter traffic / this run's time
+            unique_ran = eng.info(12) == 1 and unique_after_timed > 0
+            lay = layout_model(eng, L, unique_ran)
+            lay_dom = lay[dom]
+            dom_traffic = measured_traffic(dom, ne, L, world, op_launches[dom] / args.steps)
+            tpath, ttab = traffic_table(ne, L, world)
+            step_traffic = None
+            if ttab is not None:
+                known = {n for names in OP_ROCPROF.values() for n in names}
+                step_traffic = sum(r["hbm_bytes_per_launch"] * r["launches"] / ttab["steps"] for k, r in ttab["kernels"].items()
+                                   if kernel_base(k) in known)
+            sha_now = csrc_sha16()
+            sha_prof = (ttab or {}).get("csrc_sha16")
+
+            def per_op(op):
+                # algorithmic figure (SURVEY 8d row x points) beside the counter-measured one: the 8d rows are not lower bounds for
+                # fused passes (hypervis reads less than its row says), so "measured_GBs" is the rate to judge those by
+                ms = op_time[op] / op_launches[op]
+                tr = measured_traffic(op, ne, L, world, op_launches[op] / args.steps)
+                extra = {}
+                if op == "v_implicit":
+                    # what the column solve cannot avoid moving as designed (unique columns read once, the three solved variables
+                    # written to every stored column): the SURVEY row above also counts 26 metric doubles this kernel no longer
+                    # reads, and the measured traffic is mostly the U-row stream of the band LU going to HBM and back
+                    extra["compulsory_bytes_per_launch"] = 8.0 * ((5 * L + 1) * eng.info(1) + (3 * L + 1) * eng.info(0))
+                return {"launches_per_step": op_launches[op] / args.steps, "ms_per_launch": ms, **extra,
+                        "achieved_GBs": ALG_BYTES[op] * local_points / max(ms * 1e-3, 1e-12) / 1e9,
+                        "bytes_per_point": ALG_BYTES[op], "survey_8d_bytes_per_point": SURVEY_8D_BYTES[op],
+                        "achieved_GBs_with_survey_8d_row": SURVEY_8D_BYTES[op] * local_points / max(ms * 1e-3, 1e-12) / 1e9,
+                        "traffic": tr, "measured_GBs": (tr / max(ms * 1e-3, 1e-12) / 1e9) if tr else None,
+                        "layout_aware_bytes_per_launch": lay[op], "layout_aware_GBs": lay[op] / max(ms * 1e-3, 1e-12) / 1e9,
+                        "bound": OP_BOUND[op]}
+            out["config"].update({
+                # the sustained leg beside the K timed steps (full record: top-level "sustained")
+                "sustained_steps": sustained["steps"] if sustained else 0,
+                "sustained_ms_per_step": sustained["ms_per_step"] if sustained else None,
+                "sustained_value": (dof_per_step / (sustained["ms_per_step"] * 1e-3)) if sustained else None
+            })
+            out.update({
+                # `bound`: the roofline `frac` is priced against (HBM: every kernel of the path is fp64 stencil / band work, no GEMM); `limiter`: what
+                # limits the dominant operation as measured ("hbm", or "latency" for the column solve: dependent fp64 chains of its two co-scheduled
+                # wavefronts beside the U-row stream, see `limited_by`)
+                "roofline": {"bound": "hbm", "limiter": "hbm" if OP_BOUND[dom].startswith("hbm") else "latency", "priced_against": "hbm",
+                             "kernel": kernel_name, "operation": dom, "dominant_by": dom_note,
+                             "dominant_operation": dom_op, "operation_share_of_kernel_time": {op: round(v, 4) for op, v in op_share.items()},
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                             "points_processed_per_launch": proc_points, "points_stored": local_points,
+                             "achieved_8d_row_on_stored_points": achieved_stored, "frac_8d_row_on_stored_points": achieved_stored / HBM_PEAK_GBS,
+                             "traffic": dom_traffic, "avg_launch_ms": avg_ms,
+                             "algorithmic_bytes_per_launch": ALG_BYTES[dom] * proc_points,
+                             # (1) the same 8(d) row on the points this layout holds (the column solve works on the unique columns, not the stored ones)
+                             "achieved_8d_row_on_layout_points": (ALG_BYTES[dom] * (eng.info(1) if (unique_ran or dom == "v_implicit") else eng.info(0)) * L) / (avg_ms * 1e-3) / 1e9,
+                             "frac_8d_row_on_layout_points": (ALG_BYTES[dom] * (eng.info(1) if (unique_ran or dom == "v_implicit") else eng.info(0)) * L) / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             # (2) layout-aware algorithmic bytes: what the operation cannot avoid moving in the layout that runs (layout_model)
+                             "layout_aware_bytes_per_launch": lay_dom, "achieved_layout_aware": lay_dom / (avg_ms * 1e-3) / 1e9,
+                             "frac_layout_aware": lay_dom / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             # (3) the HBM rate itself: counter traffic of the committed PMC table / this run's launch time
+                             "hbm_rate_GBs": (dom_traffic / (avg_ms * 1e-3) / 1e9) if dom_traffic else None,
+                             "hbm_rate_frac": (dom_traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if dom_traffic else None,
+                             "traffic_over_layout_aware_bytes": (dom_traffic / lay_dom) if (dom_traffic and lay_dom) else None,
+                             "whole_step_traffic_bytes": step_traffic,
+                             "whole_step_hbm_rate_GBs": (step_traffic / (ms_per_step * 1e-3) / 1e9) if step_traffic else None,
+                             "whole_step_hbm_rate_frac": (step_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS) if step_traffic else None,
+                             "whole_step_layout_aware_GBs": sum(lay[op] * op_launches[op] / args.steps for op in lay) / (ms_per_step * 1e-3) / 1e9,
+                             "traffic_source": os.path.relpath(tpath, ROOT) if tpath else None,
+                             "traffic_source_csrc_sha16": sha_prof, "library_csrc_sha16": sha_now,
+                             "traffic_source_matches_library_sources": (sha_prof == sha_now) if sha_prof else None,
+                             "per_operation": {op: per_op(op) for op in OP_KERNELS},
+                             "limited_by": OP_BOUND[dom],
+                             "uniform_pivot_fraction": (pivot[0] / pivot[1]) if pivot[1] else None,
+                             "whole_step_algorithmic_GBs": ALG_BYTES_PER_STEP * points * args.steps / wall / 1e9,
+                             # default path: no MFMA instruction is issued (the bit-exact contractions are LDS + VALU); with TMX_MFMA=1
+                             # the fused explicit kernel issues 12 v_mfma_f64_4x4x4_4b per point: counters in profiles/r02_mfma_ab.json
+                             "mfma_utilisation": mfma["active"], "mfma_ab": mfma["ab"],
+                             "offline_sources": "traffic, mfma_utilisation and mfma_ab are read from the committed rocprofv3 passes "
+                                                "(profiles/%s_*), not measured by this run; times and rates are this run's" % PROFILE_TAG,
+                             },
+                "kernel_ms_per_step": {k: v[0] / args.steps for k, v in prof.items()},
+                "ms_per_step_with_event_markers": 1e3 * wall_prof / args.steps,
+                "state_finite": bool(state_finite),
+                "sustained": sustained,
+            })
+            if world > 1:
+                out["multi_rank"].update({"parity": parity, "per_rank_kernel_ms_per_step": rank_kernels,
+                                          "projected_from_rank_share": projected_from_rank_share(world, ne, L, ms_per_step)})
+            if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only
+                out["cpu_baseline"] = cpu_baseline(ne, L, dt, 6, 6)      # ~15 s of CPU work (1 warm-up + 6 timed steps)
+                mpi = cpu_baseline_mpi(ne, L, dt, 6)                     # + the reference's own 6-rank MPI run, ~20 core-seconds
+                if mpi is not None:
+                    out["cpu_baseline_mpi"] = mpi
+                allc = cpu_baseline_allcores(ne, L, dt, 4)              # + 24 ranks on the 24-patch layout where the host has them
+                if allc is not None:
+                    out["cpu_baseline_allcores"] = allc
+                    # the fairest host figure travels INSIDE the cpu_baseline object as well (its headline fields stay the one-core run)
+                    out["cpu_baseline"]["all_cores"] = {k: allc[k] for k in ("value", "unit", "cores", "kind", "sample") if k in allc}
+                if mpi is not None:
+                    out["cpu_baseline"]["mpi_6_ranks"] = {k: mpi[k] for k in ("value", "unit", "cores", "kind", "sample") if k in mpi}
         print(json.dumps(out))
     if world > 1:
         dist.barrier()        # peer-to-peer transport: neighbours write into this rank's block until they are done

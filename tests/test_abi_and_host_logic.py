@@ -144,6 +144,24 @@ def test_default_owner_leaves_no_rank_empty():
         default_owner(6, 8)
 
 
+def test_bench_initial_state_is_the_serial_evaluation():
+    """bench.py's initial_state (the Newton solve for eta run ahead on a thread pool) hands the timed steps the very doubles of
+    CubedSphereGrid.evaluate_test_case, and leaves the same geometry and reference state on the grid."""
+    import bench
+    from tempestmodel_amd.cubed_sphere import CubedSphereGrid, BaroclinicWaveJW
+    g1, g2 = CubedSphereGrid(6, 8, 30000.0, ppd=2), CubedSphereGrid(6, 8, 30000.0, ppd=2)
+    s1 = g1.evaluate_test_case(BaroclinicWaveJW(0.0, 30000.0, "exp"))
+    test = BaroclinicWaveJW(0.0, 30000.0, "exp")
+    s2 = bench.initial_state(g2, test)
+    assert len(s1) == len(s2) == 24 and "eta_from_z" not in vars(test)
+    for a, b in zip(s1, s2):
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    for P, Q in zip(g1.patches, g2.patches):
+        assert set(P.geom) == set(Q.geom)
+        for k in P.geom:
+            assert np.array_equal(P.geom[k], Q.geom[k]), (P.index, k)
+
+
 def test_refmath_is_glibc_bit_for_bit(tmp_path):
     """tempestmodel_amd/csrc/tmx_refmath.h (the exp / log the device evaluates in the Exner function) restates glibc's
     FMA-build exp / log; its CPU build must agree with this image's libm bit for bit: 2e7 arguments, half of them on

@@ -90,7 +90,7 @@ def test_bench_runs_as_two_rank_processes_on_one_device():
     env.pop("TMX_HALO", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--develop", "1", "--ne", "8", "--levels", "6", "--dt", "500", "--share-device", "--halo", "auto", "--no-cpu-baseline", "--sustained-steps", "50"],
+                        "--develop", "1", "--ne", "8", "--levels", "6", "--dt", "500", "--share-device", "--halo", "auto", "--full", "--no-cpu-baseline", "--sustained-steps", "50"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=400, cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]
@@ -113,7 +113,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TMX_HALO"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--develop", "1", "--ne", "8", "--levels", "6",
-                        "--dt", "500", "--share-device", "--halo", "p2p", "--no-cpu-baseline", "--sustained-steps", "0"],
+                        "--dt", "500", "--share-device", "--halo", "p2p", "--full", "--no-cpu-baseline", "--sustained-steps", "0"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=400, cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stderr[-3000:]

@@ -17,7 +17,7 @@ p = os.path.join(R, "gpurun_out", "%s_l2.sha" % tag)
 if os.path.exists(p): sha = open(p).read().strip()
 with open(os.path.join(R, "profiles", "%s_l2_lds_counters.txt" % tag), "w") as f:
     f.write("rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum  and  --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES (separate passes) -- python3 bench.py "
-            "--steps 5 --warmup 2 --develop 3 --no-cpu-baseline (ne30 L30, 1 GPU); averages per launch; kernel sources %s.\n" % sha)
+            "--steps 5 --warmup 2 --develop 3 --full --no-cpu-baseline (ne30 L30, 1 GPU); averages per launch; kernel sources %s.\n" % sha)
     f.write("l2_hit = TCC_HIT / (TCC_HIT + TCC_MISS); lds_conflict = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE (share of the LDS array's active cycles that are conflict cycles).\n\n")
     for k in sorted(set(l2) | set(lds), key=lambda k: -l2.get(k, {}).get("TCC_REQ_sum", [0, 0.0])[1]):
         a, b = l2.get(k, {}), lds.get(k, {})

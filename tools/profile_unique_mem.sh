@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 5 --warmup 2 --develop 3 --no-cpu-baseline --sustained-steps 0"
+B="$R/bench.py --steps 5 --warmup 2 --develop 3 --full --no-cpu-baseline --sustained-steps 0"
 RX="k_h_explicit|k_hypervis|k_dss|k_h_w_update"
 one() { local name=$1; shift; timeout 240 rocprofv3 "$@" --kernel-include-regex "$RX" --output-format csv -d $OUT/${TAG}_${name} -o ${TAG} -- python3 $B > $OUT/${TAG}_${name}.log 2>&1 || echo "$name failed"; }
 one rd --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum

@@ -62,7 +62,7 @@ v = counters("valu")
 if v:
     with open(os.path.join(P, "%s_valu_counters.txt" % tag), "w") as f:
         f.write("rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES -- python3 bench.py --steps 5 --warmup 2 "
-                "--develop 3 --no-cpu-baseline (ne30 L30, 1 GPU); averages per launch.\n"
+                "--develop 3 --full --no-cpu-baseline (ne30 L30, 1 GPU); averages per launch.\n"
                 "valu_active/wave_cycles = SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES (both in quad-cycles): the share of a resident wave's "
                 "life in which it issues VALU work.\n\n")
         for k, c in sorted(v.items(), key=lambda kv: -kv[1].get("SQ_BUSY_CYCLES", [0, 0])[1]):
@@ -76,7 +76,7 @@ if v:
 
 ab = {"method": "rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE and a separate "
                 "--kernel-trace --stats run, each with TMX_MFMA=0 and TMX_MFMA=1, of `python3 bench.py --steps 5 --warmup 2 --develop 3 "
-                "--no-cpu-baseline` (ne30 np4 L30, 1 GPU, element-major layout on both sides); per launch of the fused explicit kernel k_h_explicit<true,NT,MF>, summed "
+                "--full --no-cpu-baseline` (ne30 np4 L30, 1 GPU, element-major layout on both sides); per launch of the fused explicit kernel k_h_explicit<true,NT,MF>, summed "
                 "over its four instantiations of an ARS343 step (NT = 0, 4, 6, 7 combination terms).  mfma busy fraction = "
                 "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs): the share of SIMD-cycles the matrix unit is busy."}
 for env, cn, tn in (("TMX_MFMA=0", "mfma0", "trace_d"), ("TMX_MFMA=1", "mfma1", "trace_mfma1")):
