@@ -1,5 +1,5 @@
 // tmx_host.hip -- host side of the engine, part 1: C ABI set-up (life cycle, operators, patches), finalize (HBM layout, DSS groups, exchange
-// plan), state transfer, restart image, communicator and peer-to-peer set-up, introspection and options.  Part 2: tmx_step.hip.
+// plan), state transfer, restart image, communicator and peer-to-peer set-up, introspection and options.  Part 2: tmx_step.hip; part 3: tmx_program.hip.
 #include "tmx_hostshared.h"
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-// tmx_hostshared.h -- what the two host-side translation units share: tmx_host.hip (C ABI set-up: life cycle, patches, finalize and
-// its plans, state transfer, restart image, communicator set-up, introspection, options) and tmx_step.hip (the operations on the
-// resident state: stage algebra, dynamics entry points, exchange, stepper programs and their two interpreters, column physics).
+// tmx_hostshared.h -- what the three host-side translation units share: tmx_host.hip (C ABI set-up: life cycle, patches, finalize and
+// its plans, state transfer, restart image, communicator set-up, introspection, options), tmx_step.hip (the operations on the
+// resident state: stage algebra, dynamics entry points, exchange, interpolation, column physics) and tmx_program.hip (the stepper
+// programs: builder, matcher of fused units, access analysis, the element-major and node-unique interpreters, tmx_step).
 #pragma once
 #include "tmx_internal.h"
 #include <pthread.h>
@@ -91,6 +92,27 @@ int check_ready(tmx_engine * e);
 int check_inst(tmx_engine * e, int ix, bool read_only = false);
 double * inst(tmx_engine * e, int ix);
 void interp_orphan(tmx_engine * e);      // output-interpolation plans of an engine that is being destroyed
+// ... the operations the stepper programs (tmx_program.hip) launch, and the slot bookkeeping they share with the physics entry points
+const double * inst_uv(tmx_engine * e, int ix);
+void drop_readers(tmx_engine * e, int x);
+double * uinst(tmx_engine * e, int ix);
+const double * uinst_uv(tmx_engine * e, int ix);
+int u_own_uv(tmx_engine * e, int ix, bool total = false);
+void u_written(tmx_engine * e, int x);
+int surface_copy(tmx_engine * e, int src, int dst);
+int surface_zero(tmx_engine * e, int ix);
+int surface_lincomb(tmx_engine * e, int dst, int n, const double * const * src, const double * cf, int premul);
+bool stage_can_split(const tmx_engine * e);
+bool hypervis_active(const tmx_engine * e);
+int hv_step_explicit(tmx_engine * e, int iinit, int ibase, int iupd, double dt);
+int hv_step_explicit_lincomb(tmx_engine * e, int iinit, int iupd, double dt, const double * coeff, int n_coeff);
+int hv_stage_split(tmx_engine * e, int iinit, int ibase, int iupd, double dt, const double * lc, int nlc);
+int sw_stage_split(tmx_engine * e, int iinit, int ibase, int iupd, double dt);
+int copy_uv(tmx_engine * e, int src, int dst);
+int v_step_implicit_impl(tmx_engine * e, int iinit, int iupd, double dt, int itbase);
+int h_step_after_subcycle_impl(tmx_engine * e, int iinit, int iupd, int iwork, double dt, bool work_is_scratch);
+int exchange(tmx_engine * e, const KParams & p, double * x, bool * overlapped = nullptr);
+int dss_after_exchange(tmx_engine * e, const KParams & p, int ix, bool overlapped, int g_first = 0);
 // defined in tmx_host.hip
 int check_reference_state(tmx_engine * e);
 int ensure_layout(tmx_engine * e);

@@ -1,4 +1,4 @@
-// tmx_internal.h -- engine internals shared by the host side (tmx_host.hip, tmx_step.hip, tmx_unique.hip) and the kernels
+// tmx_internal.h -- engine internals shared by the host side (tmx_host.hip, tmx_step.hip, tmx_program.hip, tmx_unique.hip) and the kernels
 // (tmx_k_*.hip).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -138,7 +138,7 @@ struct UniqueLayout {
 	// becomes the instance's
 	std::vector<int> uslot; int uspare = 0;
 	// and one more for the prefix of a later stage's combination that an explicit stage forms from the instances it reads anyway
-	// (EmitTerms below, prefix_plan in tmx_step.hip); prefix_option: tmx_set_option("unique_prefix"), 1 = default since round 6 -- with the
+	// (EmitTerms below, prefix_plan in tmx_program.hip); prefix_option: tmx_set_option("unique_prefix"), 1 = default since round 6 -- with the
 	// level-parallel kernel the store of the prefix cost the producing stage what the consuming stage saved (ARS343, ne30 L30: 186.8 + 122.2 us
 	// against 144.1 + 166.7 us); the column-segment walk is bound by its streams, and 4 source instances less are 0.02-0.03 ms per step
 	int uprefix = 0, prefix_option = 1;
