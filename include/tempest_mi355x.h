@@ -498,6 +498,16 @@ int tmx_options_from_environment(tmx_engine * e);
  * what = 5: per group, 2 bits per member: the member's pairing in the reference's averaging order (groups of four,
  *           members stored as [m0, alpha partner, beta partner, diagonal]: 0 {01|23}, 1 {02|13}, 2 {03|12}; cube
  *           corners: 0 = (x + next) + previous, 1 = (x + previous) + next)
+ * The launch tables derived from these (plan-only engines hold them too):
+ * what = 6: [NS][4] per stored column its other copies, the group table inverted: the three other members in group order (-1: none),
+ *           then n | member index << 3 | pairing type << 6 | (matrix index + 1) << 8; a column in no group: -1, -1, -1, 0
+ * what = 7: early tiles of a boundary-first stage: the 64-column tiles that hold a column another rank needs
+ * what = 8: late tiles: all the others.  Both lists are empty when the stage does not split (one rank, "split_stage_off", or one of
+ *           them would be empty); tmx_info(TMX_INFO_EARLY_TILES / _LATE_TILES) counts what a device engine launches
+ * what = 9: wire layout, concatenated: send base [n_send], send stride [n_send], ghost base [n_ghost], ghost stride [n_ghost].
+ *           Buffers are [peer][slab][count of the peer]: entry t of the peer whose segment starts at off has base = nslab * off + (t - off)
+ *           and stride = count, slab s of it lies at base + s * stride
+ * what = 10: send columns [n_send], the stored column of every send-list entry
  * Returns the number of ints written (needed, when out == NULL), -1 on error. */
 int tmx_plan_get(tmx_engine * e, int what, int * out, int cap);
 /* [n_cross][4][4][4] doubles: [member m][partner q] the 2x2 matrix rotating q's (U,V) into the frame of m's patch. */

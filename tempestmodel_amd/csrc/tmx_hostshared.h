@@ -1,7 +1,9 @@
-// tmx_hostshared.h -- what the three host-side translation units share: tmx_host.hip (C ABI set-up: life cycle, patches, finalize and
-// its plans, state transfer, restart image, communicator set-up, introspection, options), tmx_step.hip (the operations on the
-// resident state: stage algebra, dynamics entry points, exchange, interpolation, column physics) and tmx_program.hip (the stepper
-// programs: builder, matcher of fused units, access analysis, the element-major and node-unique interpreters, tmx_step).
+// tmx_hostshared.h -- what the host-side translation units share: tmx_host.hip (C ABI set-up: life cycle, patches, state transfer,
+// restart image, communicator set-up, introspection), tmx_plan.hip (tmx_finalize: the plan of a rank built on the host, then uploaded;
+// plan introspection), tmx_options.hip (the option table and its four entry points), tmx_step.hip (the operations on the resident
+// state: stage algebra, dynamics entry points, exchange, interpolation, column physics), tmx_program.hip (the stepper programs:
+// builder, matcher of fused units, access analysis, the element-major and node-unique interpreters, tmx_step) and tmx_unique.hip
+// (the node-unique layout: its tables and their upload).
 #pragma once
 #include "tmx_internal.h"
 #include <pthread.h>
@@ -64,16 +66,14 @@ struct ProfScope {
 
 void prof_collect(tmx_engine * e);
 
-// plan data kept on the host for introspection (tests of the N>1 logic)
-struct PlanHost {
-	std::vector<int> grp_cols, grp_n, grp_x, grp_type;
-	std::vector<double> xmat;
-	std::vector<int> send_nodes;   // triples (patch,i,j) in send order
-	std::vector<int> recv_nodes;   // triples (patch,i,j) in ghost order
-	std::vector<int> send_cols;
-	std::vector<int> ucol, udep;
-};
-PlanHost & plan_of(tmx_engine * e);
+// host vector -> a device buffer of its own (one element at least), added to the engine's byte count
+template <class T> static int dev_upload(T ** d, const std::vector<T> & h, size_t * bytes) {
+	const size_t n = h.size() ? h.size() : 1;
+	HIPCHK(hipMalloc((void **)d, n * sizeof(T)));
+	if (h.size()) HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+	*bytes += n * sizeof(T);
+	return TMX_OK;
+}
 
 // column index of local node (i,j) (reference patch-local indices, 1-based interior) of a local patch
 static inline int col_of(const PatchInfo & P, int i, int j) {

@@ -1,4 +1,4 @@
-// tmx_internal.h -- engine internals shared by the host side (tmx_host.hip, tmx_step.hip, tmx_program.hip, tmx_unique.hip) and the kernels
+// tmx_internal.h -- engine internals shared by the host side (tmx_host.hip, tmx_plan.hip, tmx_options.hip, tmx_step.hip, tmx_program.hip, tmx_unique.hip) and the kernels
 // (tmx_k_*.hip).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -163,6 +163,22 @@ struct UniqueLayout {
 	double * d_surf_u = nullptr;             // [2][NUS] the tracked surface slots of the instance being forced, per unique column
 };
 
+// The element-major plan of a rank (tmx_plan.hip: build_plan fills it on the host, plan-only engines included; upload_plan copies what the
+// kernels read; tmx_plan_get shows it to the tests of the N > 1 logic).  In D columns; >= NS: ghost NS + index.
+struct PlanHost {
+	std::vector<int> grp_cols, grp_n, grp_x, grp_type;      // DSS groups in the engine's order
+	std::vector<double> xmat;
+	std::vector<int> send_nodes;   // triples (patch,i,j) in send order
+	std::vector<int> recv_nodes;   // triples (patch,i,j) in ghost order
+	std::vector<int> send_cols;
+	std::vector<int> ucol, udep;
+	// launch tables
+	std::vector<int> colref;                       // [NS][4] the group table inverted
+	std::vector<int> hvblocks;                     // [blocks][5] element blocks of the fused hyperviscosity kernel
+	std::vector<int> quads_early, quads_late;      // tiles of the boundary-first stages; both empty: the stage does not split
+	std::vector<int> send_base, send_stride, ghost_base, ghost_stride;      // wire layout
+};
+
 struct tmx_engine {
 	tmx_config cfg;
 	int L = 0;
@@ -310,9 +326,9 @@ struct tmx_engine {
 	int opt_h_walk_udiff = 2;                // the walk applies the horizontal uniform diffusion itself (element-major uniform-diffusion configurations): 1; 2 (default) V.StepExplicit's U,V part too; 0 = k_uniform_diffusion / k_v_explicit as passes of their own
 	int opt_hv_walk = 1;                     // hyperviscosity pass on the node-unique layout as a walk (k_hv_walk): 1 (default), 0 = the level-parallel k_hypervis
 	int opt_h_walk = -1000;                  // explicit stage on the node-unique layout: -1000 auto (column-segment walk, segments from the grid size), -n = n segments, 0 = the level-parallel kernel
-	std::vector<int> opt_default;            // default of every option, in g_options order (tmx_record_option_defaults)
 	std::vector<std::string> env_applied;    // "NAME=value" of every environment variable tmx_options_from_environment turned into an option
 	UniqueLayout u;
+	PlanHost plan;
 	bool vi_unique = false;                  // transient: the column solve runs on the unique slabs (tmxk_vi_fused)
 	ProfSlot prof_slots[TMX_K_COUNT];
 	std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> prof_pending;
@@ -324,15 +340,12 @@ void tmx_set_error(const char * fmt, ...);
 #define REQUIRE(cond, code, ...) do { if (!(cond)) { tmx_set_error(__VA_ARGS__); return (code); } } while (0)
 
 // node-unique layout (tmx_unique.hip)
-struct UniquePlanInput {      // what tmx_finalize hands over: the DSS groups in the engine's order and the send list, in D columns
-	const std::vector<int> * grp_cols, * grp_n, * grp_x, * grp_type, * send_cols;
-};
 struct UniqueTables {         // the host-side tables of the layout (tmxu_tables); thread space T = [tile][64], unique space U
 	std::vector<int> t_dcol, t_ucol, t_sdst, t_sred, tinfo, ucol_of_dcol, u_rep, slot_ucol, gsrc, gdst, gn, gx, gt, send_slots, quads_early, quads_late;
 	std::vector<int> blk_first, blk_nt, blk_info, b_sdst, b_sred, b_gsrc, b_gdst, b_gn, b_gx, b_gt, blks_early, blks_late;      // block level
 };
-int tmxu_tables(tmx_engine * e, const UniquePlanInput & in, UniqueTables & T);      // host only (works on plan-only engines)
-int tmxu_build(tmx_engine * e, const UniquePlanInput & in, size_t * bytes);
+int tmxu_tables(tmx_engine * e, UniqueTables & T);      // host only, from e->plan (works on plan-only engines)
+int tmxu_build(tmx_engine * e, size_t * bytes);         // tables + upload
 void tmxu_free(tmx_engine * e);
 KParams tmxu_params(const tmx_engine * e, const KParams & base);          // thread space T, state in U slabs
 // block kernels (archived experiment, round 6): compiled into the experiments flavour of the library only

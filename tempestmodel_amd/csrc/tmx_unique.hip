@@ -8,6 +8,7 @@
 // VerticalDynamicsFEM::StepImplicit (src/atm/VerticalDynamicsFEM.cpp:1315-1337, 1543-1633) already works on one copy per
 // patch node (the copy with local node index 0 of the upper element) and copies its result to the others.
 #include "tmx_device.h"
+#include "tmx_hostshared.h"
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -42,14 +43,6 @@ static std::vector<std::pair<int, int>> gilbert_order(int w, int h) {
 	return out;
 }
 
-template <class T> static int up(T ** d, const std::vector<T> & h, size_t * bytes) {
-	const size_t n = h.size() ? h.size() : 1;
-	HIPCHK(hipMalloc((void **)d, n * sizeof(T)));
-	if (h.size()) HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-	*bytes += n * sizeof(T);
-	return TMX_OK;
-}
-
 void tmxu_free(tmx_engine * e) {
 	UniqueLayout & u = e->u;
 	void * ptrs[] = { u.d_ustate, u.d_part, u.d_g2d_t, u.d_g2d_u, u.d_t_ucol, u.d_t_sdst, u.d_t_sred, u.d_t_tinfo, u.d_t_dcol, u.d_ucol_of_dcol, u.d_u_rep, u.d_slot_ucol,
@@ -60,10 +53,10 @@ void tmxu_free(tmx_engine * e) {
 }
 
 // Tables of the layout: host part (no device; also what tmx_debug_unique_tables hands to the CPU tests)
-int tmxu_tables(tmx_engine * e, const UniquePlanInput & in, UniqueTables & T) {
+int tmxu_tables(tmx_engine * e, UniqueTables & T) {
 	UniqueLayout & u = e->u;
 	const int NS = e->NS;
-	const std::vector<int> & gc = *in.grp_cols, & gn = *in.grp_n, & gx = *in.grp_x, & gt = *in.grp_type;
+	const std::vector<int> & gc = e->plan.grp_cols, & gn = e->plan.grp_n, & gx = e->plan.grp_x, & gt = e->plan.grp_type;
 	// ---- U numbering: patch by patch, row-major in (alpha node I, beta node J)
 	std::vector<int> ubase(e->cfg.n_patches, -1), patch_of_elem(e->ne_local, -1);
 	int nu = 0;
@@ -268,7 +261,7 @@ int tmxu_tables(tmx_engine * e, const UniquePlanInput & in, UniqueTables & T) {
 	// what other ranks need: the slots of the sent columns; tiles that hold one run before the exchange starts
 	std::vector<int> send_slots;
 	std::vector<char> early(u.NTS / 64, 0);
-	for (int c : *in.send_cols) {
+	for (int c : e->plan.send_cols) {
 		const int tc = tcol_of_dcol[c];
 		REQUIRE(slot_of_tcol[tc] >= 0, TMX_ERR_INVALID, "internal: a column another rank needs has no partial slot");
 		send_slots.push_back(slot_of_tcol[tc]); early[tc / 64] = 1;
@@ -302,10 +295,10 @@ int tmxu_tables(tmx_engine * e, const UniquePlanInput & in, UniqueTables & T) {
 }
 
 // Tables + device buffers.  Called by tmx_finalize while the host copy of the 2-D geometry still exists.
-int tmxu_build(tmx_engine * e, const UniquePlanInput & in, size_t * bytes) {
+int tmxu_build(tmx_engine * e, size_t * bytes) {
 	UniqueLayout & u = e->u;
 	UniqueTables T;
-	int r = tmxu_tables(e, in, T);
+	int r = tmxu_tables(e, T);
 	if (r) return r;
 	const int NS = e->NS;
 	// geometry in thread order and per unique column (the representative copy's)
@@ -326,15 +319,15 @@ int tmxu_build(tmx_engine * e, const UniquePlanInput & in, size_t * bytes) {
 			for (int f : rows) if (memcmp(&e->h_g2d[(size_t)f * NS + c], &e->h_g2d[(size_t)f * NS + rep], sizeof(double)) != 0) { u.vite_ok = false; break; }
 		}
 	}
-	if ((r = up(&u.d_t_tinfo, T.tinfo, bytes))) return r;
-	if ((r = up(&u.d_g2d_t, g2t, bytes)) || (r = up(&u.d_g2d_u, g2u, bytes))) return r;
-	if ((r = up(&u.d_t_ucol, T.t_ucol, bytes)) || (r = up(&u.d_t_sdst, T.t_sdst, bytes)) || (r = up(&u.d_t_sred, T.t_sred, bytes)) || (r = up(&u.d_t_dcol, T.t_dcol, bytes))) return r;
-	if ((r = up(&u.d_ucol_of_dcol, T.ucol_of_dcol, bytes)) || (r = up(&u.d_u_rep, T.u_rep, bytes)) || (r = up(&u.d_slot_ucol, T.slot_ucol, bytes))) return r;
-	if ((r = up(&u.d_gsrc, T.gsrc, bytes)) || (r = up(&u.d_gdst, T.gdst, bytes)) || (r = up(&u.d_gn, T.gn, bytes)) || (r = up(&u.d_gx, T.gx, bytes)) || (r = up(&u.d_gtype, T.gt, bytes))) return r;
-	if ((r = up(&u.d_send_slots, T.send_slots, bytes)) || (r = up(&u.d_quads_early, T.quads_early, bytes)) || (r = up(&u.d_quads_late, T.quads_late, bytes))) return r;
-	if ((r = up(&u.d_b_sdst, T.b_sdst, bytes)) || (r = up(&u.d_b_sred, T.b_sred, bytes)) || (r = up(&u.d_blk_info, T.blk_info, bytes))) return r;
-	if ((r = up(&u.d_b_gsrc, T.b_gsrc, bytes)) || (r = up(&u.d_b_gdst, T.b_gdst, bytes)) || (r = up(&u.d_b_gn, T.b_gn, bytes)) || (r = up(&u.d_b_gx, T.b_gx, bytes)) || (r = up(&u.d_b_gtype, T.b_gt, bytes))) return r;
-	if ((r = up(&u.d_blks_early, T.blks_early, bytes)) || (r = up(&u.d_blks_late, T.blks_late, bytes))) return r;
+	if ((r = dev_upload(&u.d_t_tinfo, T.tinfo, bytes))) return r;
+	if ((r = dev_upload(&u.d_g2d_t, g2t, bytes)) || (r = dev_upload(&u.d_g2d_u, g2u, bytes))) return r;
+	if ((r = dev_upload(&u.d_t_ucol, T.t_ucol, bytes)) || (r = dev_upload(&u.d_t_sdst, T.t_sdst, bytes)) || (r = dev_upload(&u.d_t_sred, T.t_sred, bytes)) || (r = dev_upload(&u.d_t_dcol, T.t_dcol, bytes))) return r;
+	if ((r = dev_upload(&u.d_ucol_of_dcol, T.ucol_of_dcol, bytes)) || (r = dev_upload(&u.d_u_rep, T.u_rep, bytes)) || (r = dev_upload(&u.d_slot_ucol, T.slot_ucol, bytes))) return r;
+	if ((r = dev_upload(&u.d_gsrc, T.gsrc, bytes)) || (r = dev_upload(&u.d_gdst, T.gdst, bytes)) || (r = dev_upload(&u.d_gn, T.gn, bytes)) || (r = dev_upload(&u.d_gx, T.gx, bytes)) || (r = dev_upload(&u.d_gtype, T.gt, bytes))) return r;
+	if ((r = dev_upload(&u.d_send_slots, T.send_slots, bytes)) || (r = dev_upload(&u.d_quads_early, T.quads_early, bytes)) || (r = dev_upload(&u.d_quads_late, T.quads_late, bytes))) return r;
+	if ((r = dev_upload(&u.d_b_sdst, T.b_sdst, bytes)) || (r = dev_upload(&u.d_b_sred, T.b_sred, bytes)) || (r = dev_upload(&u.d_blk_info, T.blk_info, bytes))) return r;
+	if ((r = dev_upload(&u.d_b_gsrc, T.b_gsrc, bytes)) || (r = dev_upload(&u.d_b_gdst, T.b_gdst, bytes)) || (r = dev_upload(&u.d_b_gn, T.b_gn, bytes)) || (r = dev_upload(&u.d_b_gx, T.b_gx, bytes)) || (r = dev_upload(&u.d_b_gtype, T.b_gt, bytes))) return r;
+	if ((r = dev_upload(&u.d_blks_early, T.blks_early, bytes)) || (r = dev_upload(&u.d_blks_late, T.blks_late, bytes))) return r;
 	u.ustride = (size_t)e->nslab * u.NUS;
 	const size_t ub = (size_t)(e->cfg.n_instances + 2) * u.ustride * sizeof(double), pb = (size_t)e->nslab * u.NP * sizeof(double);
 	HIPCHK(hipMalloc((void **)&u.d_ustate, ub)); HIPCHK(hipMemset(u.d_ustate, 0, ub)); *bytes += ub;

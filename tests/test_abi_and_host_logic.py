@@ -4,11 +4,14 @@ multi-rank exchange plan) is consistent -- exercised on 'plan only' engines (cfg
 import ctypes
 import os
 import re
+import sys
 import numpy as np
 import pytest
-import golden_util as gu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":      # run as a script (write_golden_tables below): what tests/conftest.py does under pytest
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import golden_util as gu
 
 
 def _declared_symbols():
@@ -524,3 +527,226 @@ def test_lu_flavour_probe_recognises_the_callers_dgbsv():
     finally:
         o.orc_set_lu_fma(1)
         e.close()
+
+
+# ---------------------------------------------------------------------------------------------
+# The plan tables and the option behaviour, pinned to stored results (tests/golden/plan_digests.json, option_acceptance.json).
+# Both files are written by `python tests/test_abi_and_host_logic.py` and are regenerated only together with a change that is
+# meant to alter a plan table or an option.
+
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+# (ne, L, patches, ranks, library flavour, options set before tmx_finalize); hvis_block reorders the DSS groups
+PLAN_CASES = {
+    "ne3_L5_p6_r1": (3, 5, 6, 1, None, {}),
+    "ne4_L6_p24_r3": (4, 6, 24, 3, None, {}),
+    "ne6_L6_p54_r5": (6, 6, 54, 5, None, {}),
+    "ne12_L6_p24_r3": (12, 6, 24, 3, None, {}),
+    "ne4_L6_p24_r3_experiments_hvis_block": (4, 6, 24, 3, "experiments", {"hvis_block": 1}),
+}
+_grids = {}
+
+
+def _grid(ne, L, npatch):
+    """make_grid evaluates a test case too: built once per shape, shared and left unchanged."""
+    if (ne, L, npatch) not in _grids:
+        _grids[(ne, L, npatch)] = gu.make_grid(ne, L, npatch)[0]
+    return _grids[(ne, L, npatch)]
+
+
+def _plan_digests(case):
+    """SHA-256 of every integer table a plan-only engine shows, per rank: tmx_plan_get 0-5, tmx_debug_unique_tables (tile shapes 0-4,
+    what 0-20), tmx_info 0-4 and the LENGTH of the cross-panel matrices (their doubles come from numpy's trigonometry)."""
+    import hashlib
+    from tempestmodel_amd.engine import Engine
+    ne, L, npatch, nr, flavour, options = PLAN_CASES[case]
+    buf = np.zeros(1 << 22, dtype=np.int32)
+    out = {}
+    for rank in range(nr):
+        e = Engine(_grid(ne, L, npatch), device=-2, rank=rank, n_ranks=nr, flavour=flavour, options=options)
+        e.lib.tmx_debug_unique_tables.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+        d = {}
+        for what in range(6):
+            d["plan%d" % what] = hashlib.sha256(np.ascontiguousarray(e.plan(what), dtype=np.int32).tobytes()).hexdigest()
+        for shape in range(5):
+            for what in range(21):
+                n = e.lib.tmx_debug_unique_tables(e.h, shape, what, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), len(buf))
+                assert n >= 0, (case, rank, shape, what)
+                d["unique_shape%d_what%d" % (shape, what)] = hashlib.sha256(buf[:n].tobytes()).hexdigest()
+        d["info"] = [e.info(k) for k in range(5)]
+        d["n_matrix_doubles"] = int(e.lib.tmx_plan_get_matrices(e.h, None, 0))
+        out["rank%d" % rank] = d
+        e.close()
+    return out
+
+
+@pytest.mark.parametrize("case", list(PLAN_CASES))
+def test_plan_tables_equal_the_stored_digests(case):
+    import json
+    want = json.load(open(os.path.join(GOLDEN, "plan_digests.json")))[case]
+    got = _plan_digests(case)
+    assert sorted(got) == sorted(want)
+    for rank in want:
+        diff = [k for k in want[rank] if got[rank].get(k) != want[rank][k]]
+        assert not diff and sorted(got[rank]) == sorted(want[rank]), (case, rank, diff)
+
+
+@pytest.mark.parametrize("ne,npatch,nr", [(12, 24, 3), (4, 24, 3)])
+def test_launch_tables_of_the_plan(ne, npatch, nr):
+    """The tables tmx_finalize derives from the groups and the send list (tmx_plan_get 6-10), on plan-only engines: the inverted
+    group table, the early / late tiles of the boundary-first stages and the wire layout.  ne12: several tiles per patch, the stage
+    splits; ne4: a patch is one tile and every tile holds a send column, so it does not."""
+    from tempestmodel_amd.engine import Engine
+    g = _grid(ne, 6, npatch)
+    for rank in range(nr):
+        e = Engine(g, device=-2, rank=rank, n_ranks=nr)
+        NS = int(e.plan(3)[0])
+        grp = e.plan(2).reshape(-1, 5); gx = e.plan(4); gtype = e.plan(5)
+        colref = e.plan(6).reshape(-1, 4)
+        early, late, send_cols = e.plan(7), e.plan(8), e.plan(10)
+        # ---- tiles
+        assert not set(early) & set(late)
+        if len(early) or len(late):
+            assert sorted(set(send_cols // 64)) == list(early)
+            assert sorted(list(early) + list(late)) == list(range(NS // 64)) and len(early) and len(late)
+        else:
+            assert len(np.unique(send_cols // 64)) == NS // 64      # no tile is left for the time the wire is busy
+        assert (len(early) > 0) == (ne == 12)
+        # ---- colref
+        assert colref.shape == (NS, 4)
+        seen = np.zeros(NS, dtype=bool)
+        for k in range(len(grp)):
+            n, cols = int(grp[k, 0]), grp[k, 1:]
+            for m in range(n):
+                c = int(cols[m])
+                if not 0 <= c < NS:
+                    continue      # a ghost: stored on another rank
+                others = [int(cols[o]) if o < n else -1 for o in range(4) if o != m]
+                assert list(colref[c, :3]) == others
+                assert colref[c, 3] == n | (m << 3) | (((int(gtype[k]) >> (2 * m)) & 3) << 6) | ((int(gx[k]) + 1) << 8)
+                assert not seen[c]
+                seen[c] = True
+        assert (colref[~seen] == [-1, -1, -1, 0]).all()
+        # ---- wire layout [peer][slab][count of the peer]
+        nslab = 5 * 6 + 1
+        send_rank, recv_rank = e.plan(0).reshape(-1, 4)[:, 3], e.plan(1).reshape(-1, 4)[:, 3]
+        nsend, nghost = len(send_rank), len(recv_rank)
+        assert len(send_cols) == nsend
+        wire = e.plan(9)
+        assert len(wire) == 2 * nsend + 2 * nghost
+        sb, ss, gb, gs = wire[:nsend], wire[nsend:2 * nsend], wire[2 * nsend:2 * nsend + nghost], wire[2 * nsend + nghost:]
+        for ranks, base, stride in ((send_rank, sb, ss), (recv_rank, gb, gs)):
+            assert (np.diff(ranks) >= 0).all()      # peer by peer
+            for rk in np.unique(ranks):
+                idx = np.nonzero(ranks == rk)[0]
+                off, count = int(idx[0]), len(idx)
+                assert (idx == off + np.arange(count)).all()
+                assert (base[idx] == nslab * off + np.arange(count)).all() and (stride[idx] == count).all()
+        e.close()
+
+
+# name -> environment variable of every option, in the order tmx_options_report prints them
+OPTION_ENV = (
+    ("unique_layout", "TMX_UNIQUE"), ("unique_tile_shape", "TMX_UNIQUE_TILE"), ("unique_blocks", "TMX_UNIQUE_BLOCKS"), ("unique_xcd_order", "TMX_UNIQUE_XCD"),
+    ("unique_mixed", "TMX_UNIQUE_MIXED"), ("unique_prefix", "TMX_UNIQUE_PREFIX"), ("share_copies", "TMX_SHARE_COPIES"), ("xcd_vertical", "TMX_XCD_VERTICAL"),
+    ("vi_carry", "TMX_VI_CARRY"), ("vi_pair", "TMX_VI_PAIR"), ("vi_group", "TMX_VI_GROUP"), ("vi_group_max", "TMX_VI_GROUP_MAX"), ("vi_pair_workgroup", "TMX_VI_PAIR_WG"),
+    ("vi_ring_depth", "TMX_VI_RING_DEPTH"), ("vi_producers", "TMX_VI_PRODUCERS"), ("vi_split_back", "TMX_VI_SPLIT_BACK"), ("vi_back_sub", "TMX_VI_BACK_SUB"),
+    ("vi_stagger", "TMX_VI_STAGGER_NS"), ("vi_split_kernels", "TMX_VI_MODE"), ("vi_sparse", "TMX_VI_SPARSE"), ("vi_columns_per_wavefront", "TMX_VI_CPW"),
+    ("contraction_mfma", "TMX_MFMA"), ("step_graph", "TMX_GRAPH"), ("p2p_timeout_s", "TMX_P2P_TIMEOUT_S"), ("hvis_pull", "TMX_HVIS_PULL"), ("hvis_block", "TMX_HVIS_BLOCK"),
+    ("split_stage_off", "TMX_NO_SPLIT"), ("metric_stored", "TMX_METRIC"), ("tracer_lincomb_pass", "TMX_TRACER_LINCOMB_PASS"), ("udv_separate", "TMX_UDV_SEPARATE"),
+    ("vx_fused", "TMX_VX_FUSED"), ("debug_skip_exchange", "TMX_DEBUG_SKIP_EXCHANGE"), ("exchange_overlap_off", "TMX_NO_EXCHANGE_OVERLAP"),
+    ("kessler_column", "TMX_KESSLER_COLUMN"), ("dcmip_lds", "TMX_DCMIP_LDS"), ("vt_column", "TMX_VT_COLUMN"), ("vt_explicit_v1", "TMX_VT_EXPLICIT_V1"),
+    ("vt_explicit_walk", "TMX_VT_WALK"), ("vite_walk", "TMX_VITE_WALK"), ("vx_walk", "TMX_VX_WALK"), ("vt_lanes", "TMX_VT_LANES"), ("vt_lw8", "TMX_VT_LW8"),
+    ("vt_row_lanes", "TMX_VT_NR"), ("vt_rows", "TMX_VT_ROWS"), ("lu_fma", "TMX_LU_FMA"), ("h_walk_udiff", "TMX_H_WALK_UDIFF"), ("hv_walk", "TMX_HV_WALK"), ("h_walk", "TMX_H_WALK"),
+)
+OPTION_VALUES = [-1001, -1000, -65, -64] + list(range(-3, 12)) + [16, 32, 33, 64, 65, 500, 6400, 100000]
+OPTION_ENV_STRINGS = ["0", "1", "2", "-1", "500", "stored", "split", "x"]
+
+
+def _option_sweep(flavour):
+    """What one flavour of the library does with every option: tmx_set_option's return code and the value tmx_get_option then
+    reports, over OPTION_VALUES, on a fresh engine per option before and after tmx_finalize; and what tmx_options_from_environment
+    makes of the option's variable alone, for each of OPTION_ENV_STRINGS (return value, report line, from_environment entry)."""
+    from tempestmodel_amd import engine as eng
+    lib = eng.load_library(flavour)
+    cfg = eng.TmxConfig()
+    cfg.abi_version = eng.TMX_ABI_VERSION
+    cfg.horizontal_order, cfg.vertical_order, cfg.levels, cfg.n_patches, cfg.n_instances = 4, 1, 4, 6, 7
+    cfg.hypervis_order, cfg.rank, cfg.n_ranks, cfg.device = 4, 0, 1, -2
+    cfg.element_delta_a, cfg.grav, cfg.Rd, cfg.cp, cfg.p0 = 0.1, 9.8, 287.0, 1004.5, 1e5
+
+    def report(h):
+        n = lib.tmx_options_report(h, None, 0)
+        buf = ctypes.create_string_buffer(n + 1)
+        lib.tmx_options_report(h, buf, n + 1)
+        return [l.split("=", 1) for l in buf.value.decode().splitlines()]
+
+    def sweep(h, name):
+        rows = []
+        for v in OPTION_VALUES:
+            rc = lib.tmx_set_option(h, name.encode(), ctypes.c_double(float(v)))
+            got = ctypes.c_double(-12345.0)
+            assert lib.tmx_get_option(h, name.encode(), ctypes.byref(got)) == 0
+            rows.append([int(rc), got.value])
+        return rows
+
+    names = [n for n, _ in OPTION_ENV]
+    keep = {k: os.environ.pop(k) for k in list(os.environ) if k in set(v for _, v in OPTION_ENV) or k == "TMX_QUIET"}
+    out = {"before_finalize": {}, "after_finalize": {}, "environment": {}}
+    try:
+        os.environ["TMX_QUIET"] = "1"
+        h = ctypes.c_void_p()
+        assert lib.tmx_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
+        assert [k for k, _ in report(h)] == names      # one line per option, in table order
+        lib.tmx_destroy(h)
+        g = _grid(2, 4, 6)
+        for name, var in OPTION_ENV:
+            h = ctypes.c_void_p()
+            assert lib.tmx_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
+            out["before_finalize"][name] = sweep(h, name)
+            lib.tmx_destroy(h)
+            e = eng.Engine(g, device=-2, flavour=flavour)
+            out["after_finalize"][name] = sweep(e.h, name)
+            e.close()
+            rows = []
+            for s in OPTION_ENV_STRINGS:
+                os.environ[var] = s
+                h = ctypes.c_void_p()
+                assert lib.tmx_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
+                rc = lib.tmx_options_from_environment(h)
+                r = dict(report(h))
+                rows.append([int(rc), "%s=%s" % (name, r[name]), r.get("from_environment")])
+                lib.tmx_destroy(h)
+                os.environ.pop(var)
+            out["environment"][var] = rows
+    finally:
+        os.environ.pop("TMX_QUIET", None)
+        os.environ.update(keep)
+    return out
+
+
+@pytest.mark.parametrize("flavour", ["production", "experiments"])
+def test_option_acceptance_equals_the_stored_sweep(flavour):
+    import json
+    want = json.load(open(os.path.join(GOLDEN, "option_acceptance.json")))
+    assert want["values"] == OPTION_VALUES and want["environment_strings"] == OPTION_ENV_STRINGS
+    got = json.loads(json.dumps(_option_sweep(flavour)))
+    for part in ("before_finalize", "after_finalize", "environment"):
+        assert sorted(got[part]) == sorted(want[flavour][part])
+        for k in want[flavour][part]:
+            assert got[part][k] == want[flavour][part][k], (flavour, part, k)
+
+
+def write_golden_tables():
+    """Writes tests/golden/plan_digests.json and option_acceptance.json from the libraries of THIS tree."""
+    import json
+    with open(os.path.join(GOLDEN, "plan_digests.json"), "w") as f:
+        json.dump({case: _plan_digests(case) for case in PLAN_CASES}, f, indent=0, sort_keys=True)
+        f.write("\n")
+    with open(os.path.join(GOLDEN, "option_acceptance.json"), "w") as f:
+        json.dump({"values": OPTION_VALUES, "environment_strings": OPTION_ENV_STRINGS,
+                   "production": _option_sweep("production"), "experiments": _option_sweep("experiments")}, f, sort_keys=True, separators=(",", ":"))
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    write_golden_tables()

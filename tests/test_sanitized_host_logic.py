@@ -19,7 +19,7 @@ def test_host_logic_under_address_and_undefined_behaviour_sanitizers():
     env = dict(os.environ, LD_PRELOAD=rt[-1], TMX_LIBRARY=SAN, TMX_QUIET="1",
                ASAN_OPTIONS="detect_leaks=0:verify_asan_link_order=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     # every host-logic test that needs no second library flavour and no compiler (the preloaded runtime would instrument gcc's children too)
-    skip = "not exports_every_declared and not options_are_explicit and not refmath_is_glibc"
+    skip = "not exports_every_declared and not options_are_explicit and not experiments and not refmath_is_glibc"
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_abi_and_host_logic.py"), "-x", "-q", "-p", "no:cacheprovider", "-k", skip],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=1500)
     tail = r.stdout[-4000:]
