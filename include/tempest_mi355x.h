@@ -424,7 +424,9 @@ enum {
 	TMX_INFO_PREFIX_STAGES,       /* explicit stages so far whose combination started from a partial sum an earlier stage stored */
 	TMX_INFO_EXPERIMENTS_BUILD,   /* 1: the experiments flavour of the library (archived experiments and cross-check kernels compiled in) */
 	TMX_INFO_MIXED_STEPS,         /* steps so far whose explicit stages read an element-major instance copy by copy beside node-unique ones ("unique_mixed") */
-	TMX_INFO_COLUMN_KERNEL        /* the column-solve kernel of the last launch: 0 one wavefront per column group, 1 two-wavefront pair, 2 lane group, -1 none yet */
+	TMX_INFO_COLUMN_KERNEL,       /* the column-solve kernel of the last launch: 0 one wavefront per column group, 1 two-wavefront pair, 2 lane group, -1 none yet */
+	TMX_INFO_COLUMN_VARIANT       /* ... and which variant of it: pairs per workgroup | assembly wavefronts per pair << 4 | block rows of the LDS ring << 8 for the
+	                                 two-wavefront pair (the ring depth of the instantiation that ran: 2 or 3, 4 with two assembly wavefronts), 0 for the other kernels, -1 none yet */
 };
 long long tmx_info(tmx_engine * e, int what);
 

@@ -284,6 +284,7 @@ struct tmx_engine {
 	int use_mfma = 0;                        // option "contraction_mfma" (TMX_MFMA=1): 4x4 contractions of the fused explicit kernel on the matrix unit (not bit-exact)
 	int vi_group = -1, vi_group_max = 6400;     // lane-group column kernel: -1 auto (nunique <= vi_group_max; column solve per step, group / pair kernel: 0.171 / 0.281 ms at 2 116 columns, 0.237 / 0.279 at 6 075, 0.349 / 0.279 at 8 100), 0 off, 1 on (TMX_VI_GROUP, TMX_VI_GROUP_MAX)
 	int vi_kernel_launched = -1;             // the column-solve kernel of the last launch: 0 one wavefront per column group, 1 pair (assembly || elimination), 2 lane group; -1 none yet
+	int vi_variant_launched = -1;            // ... and its variant: pairs per workgroup | assembly wavefronts per pair << 4 | block rows of the LDS ring << 8 (pair kernel), 0 (the others); -1 none yet
 	int vi_cpw = 64, vi_stream_cols = 0;     // columns per wavefront of k_vi_pair (TMX_VI_CPW; auto: fill every SIMD evenly), stream columns allocated
 	int p2p_timeout_s = 600;                 // peer-to-peer halo: how long a neighbour's message may take (TMX_P2P_TIMEOUT_S; 0 = for ever)
 	const int * stage_quads = nullptr;       // tile list of the boundary-first stage in progress (make_params -> KParams.quads)

@@ -1188,7 +1188,7 @@ __device__ __forceinline__ void ring_post(int * counter, int value, int lane) {
 // between consecutive rows (compute_block<false>: the same statements on the same operands, one more Exner evaluation per row) -- into the
 // same ring, and the elimination wavefront takes the rows in order from whichever producer made them (one `produced` counter each).  The
 // forward phase of a column group then costs the elimination chain, not the longer assembly chain.
-// RDT: block rows the ring holds (three where the LDS leaves room for two workgroups per CU with them, else two: from about 38 levels on the
+// RDT: block rows the ring holds (three where the LDS leaves room for two workgroups per CU with them, else two: from 37 levels on the
 // operator tables and three-deep rings of two pairs pass 80 KB per workgroup -- rounds 1-4 ran such grids, BASELINE config 5's 60 levels among
 // them, with ONE workgroup per CU)
 template <bool SPARSE, bool CLOSED, int PAIRS, bool BACK = true, int NPROD = 1, int RDT = TMX_RING_DEPTH>
@@ -1766,13 +1766,14 @@ void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double
 	const bool group_fits = (size_t)((e->nunique + 3) / 4) * 64 <= (size_t)TMX_UW * e->vi_stream_cols;
 	if (group_fits && (e->vi_group == 1 || (e->vi_group < 0 && e->nunique <= e->vi_group_max))) {
 		const int nwg = (e->nunique + 3) / 4;
-		e->vi_kernel_launched = 2;
+		e->vi_kernel_launched = 2; e->vi_variant_launched = 0;
 		if (p.closed) hipLaunchKernelGGL((k_vi_group<true>), dim3(nwg), dim3(64), 0, e->stream, p, xin, xup, dt, e->nunique, ucolp, udepp, e->d_ab, e->d_flag);
 		else hipLaunchKernelGGL((k_vi_group<false>), dim3(nwg), dim3(64), 0, e->stream, p, xin, xup, dt, e->nunique, ucolp, udepp, e->d_ab, e->d_flag);
 		return;
 	}
 	const bool use_pair = !TMX_EXP || (e->vi_pair == 1) || (e->vi_pair < 0 && e->vi_carry);
 	e->vi_kernel_launched = use_pair ? 1 : 0;      // (tmx_info(TMX_INFO_COLUMN_KERNEL): which kernel really ran, whatever the options asked for)
+	e->vi_variant_launched = 0;
 	const int cpw = use_pair ? e->vi_cpw : 64;
 	const int ngrp = (e->nunique + cpw - 1) / cpw;
 	if (use_pair) {
@@ -1794,6 +1795,9 @@ void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double
 		const int stagger = e->vi_stagger;
 		const int ngrp_launched = ((ngrp + pairs - 1) / pairs) * pairs;
 		const bool split = split_back && (size_t)ngrp_launched * TMX_FTOT * (p.L + 1) * sizeof(int) <= (size_t)TMX_FTOT * (p.L + 1) * e->NUS * sizeof(double);
+		// (tmx_info(TMX_INFO_COLUMN_VARIANT): pairs per workgroup, assembly wavefronts per pair and the RD of the instantiation launched below)
+		const bool two_launched = two_prod && !(TMX_EXP && split);
+		e->vi_variant_launched = pairs | (two_launched ? 2 : 1) << 4 | (two_launched ? TMX_RING_DEPTH + 1 : rdt) << 8;
 #define LAUNCH_PAIR(CL_, NP_) do { if (TMX_EXP && split) hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, TMX_EXP == 0>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_common + NP_ * lds_pair, \
 			e->stream, p, xin, xup, dt, e->nunique, e->vi_stream_cols, ucolp, udepp, e->d_ab, e->d_rhs, e->d_flag, cpw, e->d_pivot_stats, (int *)e->d_rhs, 0); \
 		else if (rdt == 2) hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, true, 1, 2>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_common + NP_ * lds_pair, \

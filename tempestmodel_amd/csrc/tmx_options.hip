@@ -45,7 +45,7 @@ static const OptionDef g_options[] = {
 	{ "vi_group", "TMX_VI_GROUP", BEFORE_FINALIZE, F(vi_group), R(-1, 1), ALL, { AS_NONZERO }, "column solve: one column per 16-lane group (-1 auto: up to vi_group_max unique columns, 0, 1)" },
 	{ "vi_group_max", "TMX_VI_GROUP_MAX", BEFORE_FINALIZE, F(vi_group_max), R(0, INT_MAX), ALL, { AS_INT }, "largest rank share (unique columns) served by the lane-group kernel (6400)" },
 	{ "vi_pair_workgroup", "TMX_VI_PAIR_WG", ANY_TIME, F(vi_pair_wg), R(0, 2), ALL, { AS_INT }, "pairs per workgroup of the two-wavefront kernel (0 auto)" },
-	{ "vi_ring_depth", "TMX_VI_RING_DEPTH", ANY_TIME, F(vi_ring_depth), ONE_OF(0, 2, 3), ALL, { AS_INT }, "block rows in the LDS ring between assembly and elimination: 0 auto (3, or 2 where only that fits two workgroups per CU: more than ~38 levels), 2, 3" },
+	{ "vi_ring_depth", "TMX_VI_RING_DEPTH", ANY_TIME, F(vi_ring_depth), ONE_OF(0, 2, 3), ALL, { AS_INT }, "block rows in the LDS ring between assembly and elimination: 0 auto (3, or 2 where only that fits two workgroups per CU: 37 to 82 levels with two pairs per workgroup), 2, 3" },
 	{ "vi_producers", "TMX_VI_PRODUCERS", ANY_TIME, F(vi_producers), R(0, 2), ALL, { AS_INT }, "assembly wavefronts per column group of that kernel: 0 auto (2 on grids that leave every wavefront a SIMD of its own), 1, 2" },
 	{ "vi_split_back", "TMX_VI_SPLIT_BACK", ANY_TIME, F(vi_split_back), ANY, DEFAULT_ONLY, { AS_INT }, "back substitution as a launch of its own (0)" },
 	{ "vi_back_sub", "TMX_VI_BACK_SUB", ANY_TIME, F(vi_back_sub), ONE_OF(1, 2, 4), DEFAULT_ONLY, { AS_INT }, "wavefronts per column group of that launch (1)" },

@@ -306,6 +306,31 @@ def test_options_are_explicit_and_reported():
         os.environ.update(old)
 
 
+def test_column_kernel_and_variant_info_before_any_launch():
+    """tmx_info(TMX_INFO_COLUMN_KERNEL) and TMX_INFO_COLUMN_VARIANT (pairs per workgroup | assembly wavefronts << 4 | ring rows << 8 of the
+    column solve's last launch) are -1 on an engine that has launched nothing; the enum in the header ends with them, at the indices the
+    GPU tests and bench.py use; an index past the enum is -1 as well.  Plan-only engine: no device needed."""
+    import re
+    from tempestmodel_amd import engine as eng
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(root, "include", "tempest_mi355x.h")).read()
+    body = hdr[hdr.index("TMX_INFO_LOCAL_COLUMNS = 0"):]
+    names = re.findall(r"^\s*(TMX_INFO_[A-Z_0-9]+)", body[:body.index("};")], re.M)
+    assert names.index("TMX_INFO_COLUMN_KERNEL") == 20 and names.index("TMX_INFO_COLUMN_VARIANT") == 21 and len(names) == 22, names
+    lib = eng.load_library()
+    cfg = eng.TmxConfig()
+    cfg.abi_version = eng.TMX_ABI_VERSION
+    cfg.horizontal_order, cfg.vertical_order, cfg.levels, cfg.n_patches, cfg.n_instances = 4, 1, 4, 6, 7
+    cfg.hypervis_order, cfg.rank, cfg.n_ranks, cfg.device = 4, 0, 1, -2
+    cfg.element_delta_a, cfg.grav, cfg.Rd, cfg.cp, cfg.p0 = 0.1, 9.8, 287.0, 1004.5, 1e5
+    h = ctypes.c_void_p()
+    assert lib.tmx_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
+    try:
+        assert [lib.tmx_info(h, k) for k in (20, 21, 22)] == [-1, -1, -1]
+    finally:
+        lib.tmx_destroy(h)
+
+
 def _unique_tables(e, shape):
     lib = e.lib
     lib.tmx_debug_unique_tables.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]

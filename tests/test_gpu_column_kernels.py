@@ -70,7 +70,7 @@ def test_row_parallel_implicit_tracer_update_is_bit_identical_to_the_column_kern
         assert any(np.abs(a - b).max() > 0 for a, b in zip(out[0][1], tr))
 
 
-@pytest.mark.parametrize("L,ud", [(6, True), (6, False), (23, True)])
+@pytest.mark.parametrize("L,ud", [(6, True), (6, False), (23, True), (40, True), (60, False)])      # (40, 60: config 4's and 5's level counts -- the default segment count comes from the grid size)
 def test_column_walking_vertical_kernels_are_bit_identical_to_the_level_parallel_ones(L, ud):
     """V.StepExplicit's U,V update, the explicitly evaluated implicit terms and the explicit tracer column update as level-parallel
     kernels (option value 0) and as column walks with sliding register windows (the default; -n: n segments per column, here also
@@ -133,7 +133,7 @@ def test_fused_column_kernels_are_bit_identical_to_split_kernels():
                 # one / two assembly wavefronts per column group (round 5: the second producer evaluates every other block row without the carry)
                 {"TMX_VI_GROUP": "0", "TMX_VI_PAIR": "1", "TMX_VI_PAIR_WG": "1", "TMX_VI_PRODUCERS": "1"},
                 {"TMX_VI_GROUP": "0", "TMX_VI_PAIR": "1", "TMX_VI_PAIR_WG": "1", "TMX_VI_PRODUCERS": "2"},
-                # ring of two / three block rows (two is what grids of more than ~38 levels get: the LDS then holds two workgroups per CU)
+                # ring of two / three block rows (two is what grids of 37 to 82 levels get with two pairs per workgroup: the LDS then holds two workgroups per CU)
                 {"TMX_VI_GROUP": "0", "TMX_VI_PAIR": "1", "TMX_VI_PAIR_WG": "2", "TMX_VI_RING_DEPTH": "2"},
                 {"TMX_VI_GROUP": "0", "TMX_VI_PAIR": "1", "TMX_VI_PAIR_WG": "1", "TMX_VI_PRODUCERS": "1", "TMX_VI_RING_DEPTH": "2"},
                 {"TMX_VI_GROUP": "0", "TMX_VI_PAIR": "1", "TMX_VI_PAIR_WG": "2", "TMX_VI_RING_DEPTH": "3"}):
