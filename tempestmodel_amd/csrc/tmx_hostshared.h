@@ -1,9 +1,10 @@
 // tmx_hostshared.h -- what the host-side translation units share: tmx_host.hip (C ABI set-up: life cycle, patches, state transfer,
 // restart image, communicator set-up, introspection), tmx_plan.hip (tmx_finalize: the plan of a rank built on the host, then uploaded;
 // plan introspection), tmx_options.hip (the option table and its four entry points), tmx_step.hip (the operations on the resident
-// state: stage algebra, dynamics entry points, exchange, interpolation, column physics), tmx_program.hip (the stepper programs:
+// state: stage algebra, the explicit stage and the hyperviscosity passes with their boundary-first loop, exchange, interpolation, column
+// physics), tmx_program.hip (the stepper programs:
 // builder, matcher of fused units, access analysis, the element-major and node-unique interpreters, tmx_step) and tmx_unique.hip
-// (the node-unique layout: its tables and their upload).
+// (the node-unique layout: its tables and their upload).  Also here: gather_terms, the one place where a coefficient vector becomes the ordered terms of a stage (StageTerms).
 #pragma once
 #include "tmx_internal.h"
 #include <pthread.h>
@@ -101,13 +102,13 @@ int u_own_uv(tmx_engine * e, int ix, bool total = false);
 void u_written(tmx_engine * e, int x);
 int surface_copy(tmx_engine * e, int src, int dst);
 int surface_zero(tmx_engine * e, int ix);
-int surface_lincomb(tmx_engine * e, int dst, int n, const double * const * src, const double * cf, int premul);
+int surface_lincomb(tmx_engine * e, const double * coeff, int n_coeff, int dst);
 bool stage_can_split(const tmx_engine * e);
 bool hypervis_active(const tmx_engine * e);
-int hv_step_explicit(tmx_engine * e, int iinit, int ibase, int iupd, double dt);
-int hv_step_explicit_lincomb(tmx_engine * e, int iinit, int iupd, double dt, const double * coeff, int n_coeff);
-int hv_stage_split(tmx_engine * e, int iinit, int ibase, int iupd, double dt, const double * lc, int nlc);
-int sw_stage_split(tmx_engine * e, int iinit, int ibase, int iupd, double dt);
+int hv_stage(tmx_engine * e, int iinit, int ibase, int iupd, double dt, const double * lc, int nlc, bool split);
+int sw_stage(tmx_engine * e, int iinit, int ibase, int iupd, double dt, bool split);
+void hvis_laplacians(tmx_engine * e, const KParams & p, const double * a, double * w);
+void hvis_apply(tmx_engine * e, const KParams & p, const double * w, const double * a, double * b, double dt, bool pull_dss = false);
 int copy_uv(tmx_engine * e, int src, int dst);
 int v_step_implicit_impl(tmx_engine * e, int iinit, int iupd, double dt, int itbase);
 int h_step_after_subcycle_impl(tmx_engine * e, int iinit, int iupd, int iwork, double dt, bool work_is_scratch);
@@ -118,3 +119,36 @@ int check_reference_state(tmx_engine * e);
 int ensure_layout(tmx_engine * e);
 int column_physics_levels(tmx_engine * e);
 struct LoopbackGroup;
+
+// Where instance m and its U,V slabs live; the return value is the instance's bit of StageTerms::dmask.  Element-major slots ...
+struct WhereD {
+	tmx_engine * e;
+	bool operator()(int m, const double *& x, const double *& x_uv) const { x = inst(e, m); x_uv = inst_uv(e, m); return false; }
+};
+// ... and node-unique ones, or the element-major slot read copy by copy for an instance of `dlive`
+struct WhereU {
+	tmx_engine * e; unsigned dlive;
+	bool operator()(int m, const double *& x, const double *& x_uv) const {
+		if (dlive >> m & 1u) { WhereD{ e }(m, x, x_uv); return true; }
+		x = uinst(e, m); x_uv = uinst_uv(e, m); return false;
+	}
+};
+// the plain base instance m (StageTerms::n == 0)
+template <class W> static StageTerms base_terms(int m, W where) {
+	StageTerms t;
+	if (where(m, t.src[0], t.src_uv[0])) t.dmask = 1u;
+	return t;
+}
+// The combination coeff[0, n_coeff) -> dst in the reference's accumulation order (GridPatch::LinearCombineData): the destination's own term,
+// then the non-zero coefficients by ascending instance index, the instances of `held` left out.  false: more than 11 source terms.
+template <class W> static bool gather_terms(StageTerms & t, const double * coeff, int n_coeff, int dst, unsigned held, W where) {
+	t = base_terms(dst, where);
+	t.n = 1; t.coef[0] = coeff[dst]; t.premul = (coeff[dst] != 0.0) ? 1 : 0;
+	for (int m = 0; m < n_coeff; m++) {
+		if (m == dst || coeff[m] == 0.0 || (held >> m & 1u)) continue;
+		if (t.n >= 12) return false;
+		if (where(m, t.src[t.n], t.src_uv[t.n])) t.dmask |= 1u << t.n;
+		t.coef[t.n++] = coeff[m];
+	}
+	return true;
+}

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/tempest_mi355x.h"
 
@@ -275,7 +276,7 @@ struct tmx_engine {
 	int vi_producers = 0;                    // assembly wavefronts per column group of the two-role column kernel: 0 auto (2 where every wavefront has a SIMD to itself), 1, 2
 	int vi_pair = -1;                        // two-wavefront column kernel (assembly || elimination): -1 auto (small grids), 0 off, 1 on (TMX_VI_PAIR)
 	// boundary-first launches (ranks > 1): 64-column tiles holding a column another rank needs, and the others
-	int * d_quads_early = nullptr, * d_quads_late = nullptr; int n_quads_early = 0, n_quads_late = 0, launch_tiles = 0; bool split_stage = false, split_overlapped = false;
+	int * d_quads_early = nullptr, * d_quads_late = nullptr; int n_quads_early = 0, n_quads_late = 0, launch_tiles = 0; bool split_stage = false;
 	int launch_blocks = 0;                   // blocks of the launch in progress (KParams::bquads), node-unique layout
 	std::vector<struct tmx_interp *> interps;          // output-interpolation plans created on this engine and not yet destroyed
 	double * d_image = nullptr; size_t image_n = 0;     // restart image of one patch (tmx_pack_active_state), grown on demand
@@ -287,7 +288,6 @@ struct tmx_engine {
 	int vi_variant_launched = -1;            // ... and its variant: pairs per workgroup | assembly wavefronts per pair << 4 | block rows of the LDS ring << 8 (pair kernel), 0 (the others); -1 none yet
 	int vi_cpw = 64, vi_stream_cols = 0;     // columns per wavefront of k_vi_pair (TMX_VI_CPW; auto: fill every SIMD evenly), stream columns allocated
 	int p2p_timeout_s = 600;                 // peer-to-peer halo: how long a neighbour's message may take (TMX_P2P_TIMEOUT_S; 0 = for ever)
-	const int * stage_quads = nullptr;       // tile list of the boundary-first stage in progress (make_params -> KParams.quads)
 	// Instance map of the stepper programs (run_program): logical data instance -> slot of d_state.  A CopyData(a -> b) whose
 	// copy stays bit-identical to its source until b is next overwritten (fully explicit vertical mode, shallow water: the
 	// V.StepImplicit that follows is a stub) is not performed; b reads a's slot instead.  Identity outside tmx_step: every
@@ -381,17 +381,46 @@ static inline bool tmxu_blocks_on(const tmx_engine * e, int which = 0) {
 // kernel launchers (tmx_k_*.hip)
 // the prefix of a later stage's combination that an explicit stage also forms and stores (emit_value in tmx_device.h)
 struct EmitTerms { double * xp; double coef[12]; int first; };
-void tmxk_h_explicit(tmx_engine * e, const KParams & p, const double * xin, const double * xbase, double * xup, double dt, int fuse_v,
-	int nterms = 0, const double * const * src = nullptr, const double * coef = nullptr, int premul = 0,
-	const double * xin_uv = nullptr, const double * xbase_uv = nullptr, const double * const * src_uv = nullptr, const EmitTerms * emit = nullptr,
-	unsigned dmask = 0u);      // dmask: LinTerms::dmask (node-unique kernels: which sources are element-major instances read per copy)
+// What an explicit stage (or a LinearCombineData) starts from, gathered on the host at every launch (gather_terms, tmx_hostshared.h).
+// n == 0: the plain base instance src[0]; n > 0: sum of coef[m] * src[m] in the reference's accumulation order -- the destination's own
+// term first (premul: its coefficient is not zero), then ascending instance index.  src_uv: where the U,V slabs of each source live (its
+// own slot or the slot it shares them with); dmask: LinTerms::dmask (node-unique kernels: which sources are element-major instances read per copy)
+struct StageTerms { int n = 0, premul = 0; unsigned dmask = 0u; const double * src[12], * src_uv[12]; double coef[12]; };
+// the same terms, `off` doubles further on (the surface slots behind an instance, its tracer slabs)
+static inline StageTerms terms_at(StageTerms t, size_t off) { for (int m = 0; m < (t.n > 0 ? t.n : 1); m++) t.src_uv[m] = t.src[m] += off; return t; }
+// -> the kernels' argument form; entries beyond n repeat entry 0 with coefficient 0 (a valid pointer for every compile-time term count)
+struct LinTerms; struct UvTerms;
+void tmxk_pack_terms(const StageTerms & t, LinTerms & x, UvTerms * uv = nullptr);
+// Run-time term count -> the compile-time one of the kernels: f(std::integral_constant<int, NT>).  0 and 2 .. 8 have instantiations of their
+// own (NT = 1 does not exist); every other count runs the largest one, CAP, on the packed entries (12: the level-parallel stage and the tracer
+// kernel; 8: the column-segment walk, which takes no more -- tmxk_h_walk_ok)
+template <int N> using TermCount = std::integral_constant<int, N>;
+template <int CAP, class F> static inline void dispatch_terms(int n, F f) {
+	switch (n) {
+		case 0: f(TermCount<0>()); break;
+		case 2: f(TermCount<2>()); break;
+		case 3: f(TermCount<3>()); break;
+		case 4: f(TermCount<4>()); break;
+		case 5: f(TermCount<5>()); break;
+		case 6: f(TermCount<6>()); break;
+		case 7: f(TermCount<7>()); break;
+		case 8: f(TermCount<8>()); break;
+		default: f(TermCount<CAP>()); break;
+	}
+}
+// ... and f(NT, PM) for the kernels that also know at compile time whether the update instance enters its own combination (premul; NT = 0:
+// no combination, launched as true)
+template <int CAP, class F> static inline void dispatch_terms_pm(int n, int premul, F f) {
+	dispatch_terms<CAP>(n, [&](auto nt) { if (decltype(nt)::value == 0 || premul) f(nt, std::true_type()); else f(nt, std::false_type()); });
+}
+// one explicit stage: xup = base + dt * rhs(xin); xin_uv: where xin's U,V slabs live; emit: also store the prefix of a later combination (or null)
+struct StageIO { const double * xin, * xin_uv; double * xup; double dt; int fuse_v; StageTerms base; const EmitTerms * emit; };
+void tmxk_h_explicit(tmx_engine * e, const KParams & p, const StageIO & s);
 // the same stage as a column-segment walk (tmx_k_hwalk.hip): node-unique layout, vertical part fused in
 bool tmxk_h_walk_ok(const tmx_engine * e, const KParams & p, int fuse_v, int nterms, bool emit);
 void tmxk_h_walk_prepare(tmx_engine * e, const KParams & p);
 int tmxk_h_walk_segments(const tmx_engine * e, const KParams & p, int ntiles, int nterms, int waves_per_simd = 0);
-void tmxk_h_walk(tmx_engine * e, const KParams & p, const double * xin, const double * xbase, double * xup, double dt, int fuse_v,
-	int nterms, const double * const * src, const double * coef, int premul, const double * xin_uv, const double * xbase_uv, const double * const * src_uv, unsigned dmask,
-	const EmitTerms * emit = nullptr);
+void tmxk_h_walk(tmx_engine * e, const KParams & p, const StageIO & s);
 bool tmxk_h_walk_fuses_udiff(const tmx_engine * e, const KParams & p, int fuse_v, int nterms);      // the walk applies the horizontal uniform diffusion itself
 bool tmxk_hv_walk_ok(const tmx_engine * e, const KParams & p);      // the hyperviscosity pass as a walk (same file)
 void tmxk_hv_walk(tmx_engine * e, const KParams & p, const double * xsrc, const double * xbase, double * xout, double dt, double nu_s, double nu_d, double nu_v, int scale);
@@ -406,7 +435,7 @@ void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xi
 void tmxk_dss(tmx_engine * e, const KParams & p, double * x, int g0, int g1);
 void tmxk_hypervis(tmx_engine * e, const KParams & p, const double * xsrc, const double * xbase, double * xout,
 	double dt, double nu_s, double nu_d, double nu_v, int scale_locally, bool pull_dss = false);
-void tmxk_lincomb(tmx_engine * e, size_t n, double * dst, int nterms, const double * const * src, const double * coef, int dst_is_term0);
+void tmxk_lincomb(tmx_engine * e, size_t n, double * dst, const StageTerms & t);      // dst = t (term 0 is dst itself)
 void tmxk_pack(tmx_engine * e, const KParams & p, const double * x);
 void tmxk_pack_p2p(tmx_engine * e, const KParams & p, const double * x, int buf);
 void tmxk_p2p_signal_wait(tmx_engine * e, hipStream_t s, int buf, unsigned long long seq);
@@ -421,8 +450,7 @@ enum { DC_RA0 = 0, DC_RA1, DC_RB0, DC_RB1, DC_RCOS, DC_ADIV, DC_AA0, DC_AA1, DC_
 size_t tmxk_dcmip_lds_bytes(int L);
 void tmxk_dcmip(tmx_engine * e, const KParams & p, double * x, double dt, int test, int pbl, int prec, double earth_radius, bool lds);
 // tracers (rows H8 / V8)
-void tmxk_h_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * xbase, double * xup, double dt,
-	int nterms = 0, const double * const * src = nullptr, const double * coef = nullptr, int premul = 0, const double * xin_uv = nullptr);
+void tmxk_h_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * xin_uv, const StageTerms & base, double * xup, double dt);
 void tmxk_hypervis_block(tmx_engine * e, const KParams & p, const double * xsrc, const double * xbase, double * xout,
 	double dt, double nu_s, double nu_d, double nu_v, int scale_locally);
 void tmxk_hypervis_tracers(tmx_engine * e, const KParams & p, const double * xsrc, const double * xbase, double * xout, double dt, double nu, int filter, int scale_locally);

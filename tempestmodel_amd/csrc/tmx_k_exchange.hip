@@ -237,10 +237,19 @@ __global__ __launch_bounds__(256) void k_lincomb(size_t n, double * __restrict__
 	}
 }
 
-void tmxk_lincomb(tmx_engine * e, size_t n, double * dst, int nterms, const double * const * src, const double * coef, int premul) {
+// the terms of a stage in the kernels' argument form: entries beyond n repeat entry 0 with coefficient 0 (n == 0: the base instance alone)
+void tmxk_pack_terms(const StageTerms & t, LinTerms & x, UvTerms * uv) {
+	x.n = t.n; x.premul = t.premul; x.dmask = t.dmask;
+	for (int m = 0; m < 12; m++) {
+		const int s = (m < t.n) ? m : 0;
+		x.src[m] = t.src[s]; x.coef[m] = (m < t.n) ? t.coef[m] : 0.0;
+		if (uv) uv->src[m] = t.src_uv[s];
+	}
+}
+
+void tmxk_lincomb(tmx_engine * e, size_t n, double * dst, const StageTerms & terms) {
 	LinTerms t;
-	t.n = nterms; t.premul = premul;
-	for (int m = 0; m < nterms; m++) { t.src[m] = src[m]; t.coef[m] = coef[m]; }
+	tmxk_pack_terms(terms, t);
 	const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
 	hipLaunchKernelGGL(k_lincomb, dim3(blocks), dim3(256), 0, e->stream, n, dst, t);
 }

@@ -502,24 +502,16 @@ __global__ __launch_bounds__(256) void k_h_w_update(KParams p, LinTerms xbase, d
 		xup[TMX_SLAB_W(L, k) * NS + col] = wnew;
 }
 
-// xin_uv / xbase_uv / src_uv: where the U,V slabs of the initial instance, the base instance and the combination sources
-// live when that is not the instance's own slot (NULL: the same pointers)
-void tmxk_h_explicit(tmx_engine * e, const KParams & p, const double * xin, const double * xbase_ptr, double * xup, double dt, int fuse_v,
-	int nterms, const double * const * src, const double * coef, int premul, const double * xin_uv, const double * xbase_uv, const double * const * src_uv,
-	const EmitTerms * emit, unsigned dmask) {
+void tmxk_h_explicit(tmx_engine * e, const KParams & p, const StageIO & st) {
+	const double * xin = st.xin; double * xup = st.xup;
+	const double dt = st.dt; const int fuse_v = st.fuse_v, nterms = st.base.n, premul = st.base.premul; const unsigned dmask = st.base.dmask;
+	const EmitTerms * emit = st.emit;
 	// the column-segment walk (tmx_k_hwalk.hip) does the whole stage, W of every interface included (node-unique layout: with the vertical part fused in)
-	if (tmxk_h_walk_ok(e, p, fuse_v, nterms, emit && emit->xp)) {
-		tmxk_h_walk(e, p, xin, xbase_ptr, xup, dt, fuse_v, nterms, src, coef, premul, xin_uv, xbase_uv, src_uv, dmask, emit);
-		return;
-	}
+	if (tmxk_h_walk_ok(e, p, fuse_v, nterms, emit && emit->xp)) { tmxk_h_walk(e, p, st); return; }
 	// base of the update: a plain instance (nterms == 0) or a linear combination evaluated in the kernels
 	LinTerms xbase;
 	UvTerms uvt;
-	xbase.n = nterms; xbase.premul = premul; xbase.dmask = dmask;
-	xbase.src[0] = xbase_ptr; xbase.coef[0] = 0.0;
-	uvt.xin = xin_uv ? xin_uv : xin; uvt.src[0] = xbase_uv ? xbase_uv : xbase_ptr;
-	for (int m = 0; m < nterms; m++) { xbase.src[m] = src[m]; xbase.coef[m] = coef[m]; uvt.src[m] = src_uv ? src_uv[m] : src[m]; }
-	for (int m = (nterms > 0 ? nterms : 1); m < 12; m++) { xbase.src[m] = xbase.src[0]; xbase.coef[m] = 0.0; uvt.src[m] = uvt.src[0]; }
+	tmxk_pack_terms(st.base, xbase, &uvt); uvt.xin = st.xin_uv;
 	const int ntile = p.quads ? e->launch_tiles : p.NS / 64;
 	const bool uq = p.t_ucol != nullptr;      // node-unique layout (tmxu_params): 1-D launches, XCD-aware tile order
 	if (uq) e->u.slots_by_blocks = false;      // (wavefront-level seam exchange: the DSS kernel runs its full list)
@@ -537,33 +529,21 @@ void tmxk_h_explicit(tmx_engine * e, const KParams & p, const double * xin, cons
 	// (the prefix of a later stage's combination: node-unique layout with the vertical part fused in, no own coefficient, at least two terms)
 	const bool emit_ok = TMX_EXP && emit && emit->xp && uq && fuse_v && !premul && nterms >= 3 && nterms <= 8;
 	const EmitTerms em = emit_ok ? *emit : em0;
-#define LAUNCH_HV2(NT_, PM_) do { \
-		if (TMX_EXP && uq && fuse_v && emit_ok && NT_ >= 3 && NT_ <= 8 && !PM_) hipLaunchKernelGGL((k_h_explicit<true, (NT_ >= 3 && NT_ <= 8) ? NT_ : 3, false, true, false, TMX_EXP != 0>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em); \
-		else if (uq && fuse_v && dmask) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, true, PM_, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0); \
-		else if (uq && fuse_v) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, true, PM_, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0); \
-		else if (uq) hipLaunchKernelGGL((k_h_explicit<false, NT_, false, true, PM_, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0); \
-		else if (fuse_v && e->use_mfma) hipLaunchKernelGGL((k_h_explicit<true, NT_, true, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0); \
-		else if (fuse_v) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0); \
-		else hipLaunchKernelGGL((k_h_explicit<false, NT_, false, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0); } while (0)
-#define LAUNCH_HV(NT_) do { \
-		if (NT_ == 0 || premul) LAUNCH_HV2(NT_, true); else LAUNCH_HV2(NT_, false); \
-		if (TMX_EXP && uq && emit_ok && NT_ >= 3 && NT_ <= 8) hipLaunchKernelGGL((k_h_w_update<(NT_ >= 3 && NT_ <= 8) ? NT_ : 3, true, TMX_EXP != 0>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em); \
-		else if (uq && dmask) hipLaunchKernelGGL((k_h_w_update<NT_, true, false, true>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0); \
-		else if (uq) hipLaunchKernelGGL((k_h_w_update<NT_, true, false>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0); \
-		else hipLaunchKernelGGL((k_h_w_update<NT_, false, false>), grd2, blk2, 0, e->stream, p, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0); } while (0)
-	switch (nterms) {
-		case 0: LAUNCH_HV(0); break;
-		case 2: LAUNCH_HV(2); break;
-		case 3: LAUNCH_HV(3); break;
-		case 4: LAUNCH_HV(4); break;
-		case 5: LAUNCH_HV(5); break;
-		case 6: LAUNCH_HV(6); break;
-		case 7: LAUNCH_HV(7); break;
-		case 8: LAUNCH_HV(8); break;
-		default: LAUNCH_HV(12); break;      // entries beyond n carry coefficient 0 and a valid pointer (see below)
-	}
-#undef LAUNCH_HV
-#undef LAUNCH_HV2
+	dispatch_terms_pm<12>(nterms, premul, [&](auto nt, auto pm) {
+		constexpr int NT_ = decltype(nt)::value; constexpr bool PM_ = decltype(pm)::value;
+		if (TMX_EXP && uq && fuse_v && emit_ok && NT_ >= 3 && NT_ <= 8 && !PM_) hipLaunchKernelGGL((k_h_explicit<true, (NT_ >= 3 && NT_ <= 8) ? NT_ : 3, false, true, false, TMX_EXP != 0>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em);
+		else if (uq && fuse_v && dmask) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, true, PM_, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
+		else if (uq && fuse_v) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, true, PM_, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
+		else if (uq) hipLaunchKernelGGL((k_h_explicit<false, NT_, false, true, PM_, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
+		else if (fuse_v && e->use_mfma) hipLaunchKernelGGL((k_h_explicit<true, NT_, true, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
+		else if (fuse_v) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
+		else hipLaunchKernelGGL((k_h_explicit<false, NT_, false, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
+		// ... and W of the interfaces the stage's kernel left
+		if (TMX_EXP && uq && emit_ok && NT_ >= 3 && NT_ <= 8) hipLaunchKernelGGL((k_h_w_update<(NT_ >= 3 && NT_ <= 8) ? NT_ : 3, true, TMX_EXP != 0>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em);
+		else if (uq && dmask) hipLaunchKernelGGL((k_h_w_update<NT_, true, false, true>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0);
+		else if (uq) hipLaunchKernelGGL((k_h_w_update<NT_, true, false>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0);
+		else hipLaunchKernelGGL((k_h_w_update<NT_, false, false>), grd2, blk2, 0, e->stream, p, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0);
+	});
 }
 
 // HorizontalDynamicsFEM::ApplyRayleighFriction (src/atm/HorizontalDynamicsFEM.cpp:2420-2570): where the strength
@@ -719,30 +699,15 @@ __global__ __launch_bounds__(256) void k_h_tracers(KParams p, int nt, const doub
 	}
 }
 
-void tmxk_h_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * xbase_ptr, double * xup, double dt,
-	int nterms, const double * const * src, const double * coef, int premul, const double * xin_uv) {
-	if (!xin_uv) xin_uv = xin;
+void tmxk_h_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * xin_uv, const StageTerms & base, double * xup, double dt) {
 	LinTerms xbase;
-	xbase.n = nterms; xbase.premul = premul;
-	xbase.src[0] = xbase_ptr; xbase.coef[0] = 0.0;
-	for (int m = 0; m < nterms; m++) { xbase.src[m] = src[m]; xbase.coef[m] = coef[m]; }
-	for (int m = (nterms > 0 ? nterms : 1); m < 12; m++) { xbase.src[m] = xbase.src[0]; xbase.coef[m] = 0.0; }
+	tmxk_pack_terms(base, xbase);
 	dim3 blk(64, 4), grd(NTILES(e, p), (p.L + 3) / 4);
-#define LAUNCH_HT(NT_) do { \
-		if (e->udiff) hipLaunchKernelGGL((k_h_tracers<true, NT_>), grd, blk, 0, e->stream, p, e->nt, (const double *)e->d_area, xin, xbase, xup, dt, e->cfg.uniform_diffusion_scalar, xin_uv); \
-		else hipLaunchKernelGGL((k_h_tracers<false, NT_>), grd, blk, 0, e->stream, p, e->nt, (const double *)e->d_area, xin, xbase, xup, dt, 0.0, xin_uv); } while (0)
-	switch (nterms) {
-		case 0: LAUNCH_HT(0); break;
-		case 2: LAUNCH_HT(2); break;
-		case 3: LAUNCH_HT(3); break;
-		case 4: LAUNCH_HT(4); break;
-		case 5: LAUNCH_HT(5); break;
-		case 6: LAUNCH_HT(6); break;
-		case 7: LAUNCH_HT(7); break;
-		case 8: LAUNCH_HT(8); break;
-		default: LAUNCH_HT(12); break;      // entries beyond n carry coefficient 0 and a valid pointer, as in tmxk_h_explicit
-	}
-#undef LAUNCH_HT
+	dispatch_terms<12>(base.n, [&](auto nt) {
+		constexpr int NT_ = decltype(nt)::value;
+		if (e->udiff) hipLaunchKernelGGL((k_h_tracers<true, NT_>), grd, blk, 0, e->stream, p, e->nt, (const double *)e->d_area, xin, xbase, xup, dt, e->cfg.uniform_diffusion_scalar, xin_uv);
+		else hipLaunchKernelGGL((k_h_tracers<false, NT_>), grd, blk, 0, e->stream, p, e->nt, (const double *)e->d_area, xin, xbase, xup, dt, 0.0, xin_uv);
+	});
 }
 
 // ApplyScalarHyperdiffusion, tracer branch (HorizontalDynamicsFEM.cpp:1999-2035, :2076-2165) and, after the second

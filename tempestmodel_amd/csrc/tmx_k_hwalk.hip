@@ -667,16 +667,13 @@ void tmxk_h_walk_prepare(tmx_engine * e, const KParams & p) {
 	if (e->udiff && !e->refd_valid && e->d_ref && tmxk_h_walk_fuses_udiff(e, p, 0, 0)) (void)ref_diffusion_terms(e, p);
 }
 
-void tmxk_h_walk(tmx_engine * e, const KParams & p, const double * xin, const double * xbase_ptr, double * xup, double dt, int fuse_v,
-	int nterms, const double * const * src, const double * coef, int premul, const double * xin_uv, const double * xbase_uv, const double * const * src_uv, unsigned dmask,
-	const EmitTerms * emit) {
+void tmxk_h_walk(tmx_engine * e, const KParams & p, const StageIO & st) {
+	const double * xin = st.xin; double * xup = st.xup;
+	const double dt = st.dt; const int fuse_v = st.fuse_v, nterms = st.base.n, premul = st.base.premul; const unsigned dmask = st.base.dmask;
+	const EmitTerms * emit = st.emit;
 	LinTerms xbase;
 	UvTerms uvt;
-	xbase.n = nterms; xbase.premul = premul; xbase.dmask = dmask;
-	xbase.src[0] = xbase_ptr; xbase.coef[0] = 0.0;
-	uvt.xin = xin_uv ? xin_uv : xin; uvt.src[0] = xbase_uv ? xbase_uv : xbase_ptr;
-	for (int m = 0; m < nterms; m++) { xbase.src[m] = src[m]; xbase.coef[m] = coef[m]; uvt.src[m] = src_uv ? src_uv[m] : src[m]; }
-	for (int m = (nterms > 0 ? nterms : 1); m < 12; m++) { xbase.src[m] = xbase.src[0]; xbase.coef[m] = 0.0; uvt.src[m] = uvt.src[0]; }
+	tmxk_pack_terms(st.base, xbase, &uvt); uvt.xin = st.xin_uv;
 	const int ntile = p.quads ? e->launch_tiles : p.NS / 64;
 	// (the kernels that apply the uniform diffusion hold 190 - 256 registers whatever the number of terms: two wavefronts per SIMD)
 	// (three wavefronts per SIMD -- at most 168 registers -- for the plain stage and the two-term combination without a coefficient of its own)
@@ -690,24 +687,13 @@ void tmxk_h_walk(tmx_engine * e, const KParams & p, const double * xin, const do
 		// (fuse_v with uniform diffusion: the vertical diffusion of U, V rides along where k_v_explicit_slide would apply it -- the fully explicit mode)
 		const UdiffArgs ud0 = { nullptr, 0.0, 0.0, nullptr, 0.0, 0 }, ud1 = { (const double *)e->d_ref, e->cfg.uniform_diffusion_scalar, e->cfg.uniform_diffusion_vector,
 			udf ? ref_diffusion_terms(e, p) : nullptr, e->cfg.uniform_diffusion_vector / (e->cfg.ztop * e->cfg.ztop), (e->fully_explicit && !e->opt_udv_separate) ? 1 : 0 };
-#define LAUNCH_D2(NT_, PM_) do { \
-			if (fuse_v && udf) hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, true, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud1); \
-			else if (fuse_v) hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud0); \
-			else if (udf) hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud1); \
-			else hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud0); } while (0)
-#define LAUNCH_D(NT_) do { if (NT_ == 0 || premul) LAUNCH_D2(NT_, true); else LAUNCH_D2(NT_, false); } while (0)
-		switch (nterms) {
-			case 0: LAUNCH_D(0); break;
-			case 2: LAUNCH_D(2); break;
-			case 3: LAUNCH_D(3); break;
-			case 4: LAUNCH_D(4); break;
-			case 5: LAUNCH_D(5); break;
-			case 6: LAUNCH_D(6); break;
-			case 7: LAUNCH_D(7); break;
-			default: LAUNCH_D(8); break;
-		}
-#undef LAUNCH_D
-#undef LAUNCH_D2
+		dispatch_terms_pm<8>(nterms, premul, [&](auto nt, auto pm) {
+			constexpr int NT_ = decltype(nt)::value; constexpr bool PM_ = decltype(pm)::value;
+			if (fuse_v && udf) hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, true, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud1);
+			else if (fuse_v) hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud0);
+			else if (udf) hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud1);
+			else hipLaunchKernelGGL((k_h_walk<NT_, PM_, false, false, false, false, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em1, ud0);
+		});
 		return;
 	}
 	// block kernels: the launch is over the blocks of the thread order (four wavefronts each), the seams between a block's wavefronts never reach the partial slots
@@ -721,25 +707,15 @@ void tmxk_h_walk(tmx_engine * e, const KParams & p, const double * xin, const do
 	// (the prefix of a later stage's combination: no own coefficient, three to eight terms, node-unique sources, wavefront-level kernel)
 	const bool emit_ok = emit && emit->xp && !premul && !dmask && !blocks && nterms >= 3 && nterms <= 8;
 	const EmitTerms em = emit_ok ? *emit : em0;
-#define LAUNCH_W3(NT_, PM_, DM_) do { \
-		if (emit_ok && NT_ >= 3 && !PM_ && !DM_) hipLaunchKernelGGL((k_h_walk<(NT_ >= 3 ? NT_ : 3), false, false, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em, udn); \
-		else if (TMX_EXP && blocks) hipLaunchKernelGGL((k_h_walk<NT_, PM_, DM_, TMX_EXP != 0>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em0, udn); \
-		else hipLaunchKernelGGL((k_h_walk<NT_, PM_, DM_, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em0, udn); } while (0)
-#define LAUNCH_W2(NT_, PM_) do { if (dmask) LAUNCH_W3(NT_, PM_, true); else LAUNCH_W3(NT_, PM_, false); } while (0)
-#define LAUNCH_W(NT_) do { if (NT_ == 0 || premul) LAUNCH_W2(NT_, true); else LAUNCH_W2(NT_, false); } while (0)
-	switch (nterms) {
-		case 0: LAUNCH_W(0); break;
-		case 2: LAUNCH_W(2); break;
-		case 3: LAUNCH_W(3); break;
-		case 4: LAUNCH_W(4); break;
-		case 5: LAUNCH_W(5); break;
-		case 6: LAUNCH_W(6); break;
-		case 7: LAUNCH_W(7); break;
-		default: LAUNCH_W(8); break;
-	}
-#undef LAUNCH_W3
-#undef LAUNCH_W
-#undef LAUNCH_W2
+	dispatch_terms_pm<8>(nterms, premul, [&](auto nt, auto pm) {
+		auto launch = [&](auto dm) {
+			constexpr int NT_ = decltype(nt)::value; constexpr bool PM_ = decltype(pm)::value, DM_ = decltype(dm)::value;
+			if (emit_ok && NT_ >= 3 && !PM_ && !DM_) hipLaunchKernelGGL((k_h_walk<(NT_ >= 3 ? NT_ : 3), false, false, false, true>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em, udn);
+			else if (TMX_EXP && blocks) hipLaunchKernelGGL((k_h_walk<NT_, PM_, DM_, TMX_EXP != 0>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em0, udn);
+			else hipLaunchKernelGGL((k_h_walk<NT_, PM_, DM_, false>), grd, blk, 0, e->stream, q, xin, xbase, xup, dt, uvt, nseg, em0, udn);
+		};
+		if (dmask) launch(std::true_type()); else launch(std::false_type());
+	});
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -289,7 +289,7 @@ static void build_launch_tables(tmx_engine * e) {
 	// Boundary-first launches (north-star: "exchange overlapped with interior-element updates").  A 64-column tile (four
 	// elements) is EARLY when it holds a column some other rank needs; the kernels that feed an exchange run on the early
 	// tiles first, the pack + grouped send/recv starts on the exchange stream, and the remaining tiles -- three quarters
-	// of a 15 x 15-element patch -- are updated while the wire is busy (hv_stage_split).  TMX_NO_SPLIT=1 switches it off.
+	// of a 15 x 15-element patch -- are updated while the wire is busy (produce_and_average, tmx_step.hip).  TMX_NO_SPLIT=1 switches it off.
 	// The stage splits when both lists have tiles; otherwise both stay empty.
 	if (NR > 1 && !plan.send_cols.empty() && !e->opt_no_split) {
 		std::vector<char> early(e->NS / 64, 0);

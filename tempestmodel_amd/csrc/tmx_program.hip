@@ -397,19 +397,13 @@ static int run_stage(tmx_engine * e, const Unit & u, size_t * ops) {
 		// evaluated inside the explicit kernels; H + V alone: b += c * rhs(i)
 		if (!u.same_coef || ((u.from_copy || u.lc) && u.init == u.upd)) return TMX_OK;
 		*ops = u.n_ops + (split ? 1 : 0);
-		if (split) return RUN(hv_stage_split(e, u.init, u.base, u.upd, u.coef, u.lc, u.nlc));
-		if (u.lc) return RUN(hv_step_explicit_lincomb(e, u.init, u.upd, u.coef, u.lc, u.nlc));
-		return RUN(hv_step_explicit(e, u.init, u.base, u.upd, u.coef));
+		return RUN(hv_stage(e, u.init, u.base, u.upd, u.coef, u.lc, u.nlc, split));
 	}
 	// shallow water, no tracers: Copy(a->b) + H(i,b,c) [+ V stub]: out = a + c * rhs(i) in one pass (k_sw_explicit takes the base
 	// apart); H [+ V stub] in place only as a boundary-first stage (otherwise H's own launch is all there is)
 	if (u.lc || u.init == u.upd || (u.from_copy ? (e->nt != 0 || u.base == u.upd) : !split)) return TMX_OK;
 	*ops = u.n_ops + (split ? 1 : 0);
-	if (split) return RUN(sw_stage_split(e, u.init, u.base, u.upd, u.coef));
-	if (e->dry_run) return TMX_OK;
-	ProfScope ps(e, TMX_K_H_EXPLICIT);
-	tmxk_sw_explicit(e, make_params(e), inst(e, u.init), inst(e, u.base), inst(e, u.upd), u.coef);
-	return launch_check("sw copy + H");
+	return RUN(sw_stage(e, u.init, u.base, u.upd, u.coef, split));
 }
 
 // dry_unsafe: see Access
@@ -687,67 +681,49 @@ extern "C" int tmx_debug_program_prefix(int scheme, int first_step, int last_ste
 // [Copy(ibase -> iupd) | LinearCombine(lc -> iupd)]; H.StepExplicit(iinit, iupd); V.StepExplicit(iinit, iupd); DSS(iupd)
 // emit: also store the prefix of a later stage's combination; held: members of the stored prefix this stage's combination starts from
 static int u_stage(tmx_engine * e, int iinit, int ibase, int iupd, double dt, const double * lc, int nlc, const PrefixPlan * emit = nullptr, unsigned held = 0u) {
-	const double * src[12]; double cf[12]; int premul = 0, n = 0;
-	const double * srcuv[12];
 	double * const prefix = e->u.d_ustate + (size_t)e->u.uprefix * e->u.ustride;
 	// instances read in element-major form, copy by copy (UniqueLayout::dlive): their pointers are the element-major slots', the kernels get a mask
-	auto dl = [&](int k) -> bool { return (e->u.dlive >> k & 1u) != 0u; };
-	unsigned dmask = 0u;
+	const WhereU where = { e, e->u.dlive };
+	// (all pointers are taken here, before the update instance changes slots)
+	StageIO st; st.dt = dt; st.fuse_v = 1; st.emit = nullptr;
+	StageTerms & t = st.base;
 	if (lc) {
-		premul = (lc[iupd] != 0.0) ? 1 : 0;
-		n = 1; src[0] = dl(iupd) ? inst(e, iupd) : uinst(e, iupd); srcuv[0] = dl(iupd) ? inst_uv(e, iupd) : uinst_uv(e, iupd); cf[0] = lc[iupd];
-		if (dl(iupd)) dmask |= 1u;
-		if (held) { src[0] = srcuv[0] = prefix; cf[0] = 1.0; premul = 1; e->u.prefix_stages++; }      // (times one: exact)
-		for (int m = 0; m < nlc; m++) {
-			if (m == iupd || lc[m] == 0.0 || (held >> m & 1u)) continue;
-			REQUIRE(n < 12, TMX_ERR_UNSUPPORTED, "linear combination with more than 11 source terms");
-			src[n] = dl(m) ? inst(e, m) : uinst(e, m); srcuv[n] = dl(m) ? inst_uv(e, m) : uinst_uv(e, m); cf[n] = lc[m];
-			if (dl(m)) dmask |= 1u << n;
-			n++;
-		}
-	} else if (dl(ibase)) dmask |= 1u;
-	if (dl(iinit)) dmask |= 1u << 31;
+		REQUIRE(gather_terms(t, lc, nlc, iupd, held, where), TMX_ERR_UNSUPPORTED, "linear combination with more than 11 source terms");
+		if (held) { t.src[0] = t.src_uv[0] = prefix; t.coef[0] = 1.0; t.premul = 1; e->u.prefix_stages++; }      // (times one: exact)
+	} else t = base_terms(ibase, where);
+	if (where(iinit, st.xin, st.xin_uv)) t.dmask |= 1u << 31;
+	const int n = t.n; const unsigned dmask = t.dmask;
 	REQUIRE(!(held && dmask), TMX_ERR_UNSUPPORTED, "internal: stored prefix with element-major sources");
 	REQUIRE(!dmask || e->u.tile_shape == 0 || tmxk_h_walk_ok(e, tmxu_params(e, make_params(e)), 1, n, false), TMX_ERR_UNSUPPORTED,
 		"internal: copy-by-copy reads of an element-major instance with this thread order need the column-segment walk");
-	const double * xin_uv = dl(iinit) ? inst_uv(e, iinit) : uinst_uv(e, iinit), * base_uv = dl(ibase) ? inst_uv(e, ibase) : uinst_uv(e, ibase);      // (taken before the update instance changes slots)
 	// the update instance is also read (in-place accumulation, or its own coefficient in the combination is not zero): the
 	// element-major kernels read and write a thread's own column, here other elements' threads read the node too -- write the
 	// spare slot and let it become the instance's
-	bool aliased = lc ? (premul != 0) : (ibase == iupd);
+	bool aliased = lc ? (t.premul != 0) : (ibase == iupd);
 	if (held) {      // the destination's own term is inside the prefix: its slot is read only if something else lives there
 		const double * mine = uinst(e, iupd);
-		aliased = xin_uv == mine;
-		for (int m = 1; m < n; m++) aliased = aliased || src[m] == mine || srcuv[m] == mine;
+		aliased = st.xin_uv == mine;
+		for (int m = 1; m < n; m++) aliased = aliased || t.src[m] == mine || t.src_uv[m] == mine;
 	}
 	REQUIRE(iinit != iupd, TMX_ERR_INVALID, "StepExplicit: initial and update data instance must be distinct");
-	double * out = aliased ? uspare(e) : uinst(e, iupd);
-	const double * base = lc ? nullptr : (dl(ibase) ? inst(e, ibase) : uinst(e, ibase)), * xin = dl(iinit) ? inst(e, iinit) : uinst(e, iinit);
+	st.xup = aliased ? uspare(e) : uinst(e, iupd);
 	EmitTerms em; em.xp = nullptr; em.first = -1;
 	// (only a kernel that really stores it: the column-segment walk, or the level-parallel kernel of the experiments flavour; element-major sources: no prefix)
 	const bool walk = tmxk_h_walk_ok(e, tmxu_params(e, make_params(e)), 1, n, true);
-	if (emit && lc && !premul && n >= 3 && n <= 8 && !dmask && (walk ? !tmxu_blocks_on(e, 1) : TMX_EXP != 0)) {      // (the block form of the walk stores none)
+	if (emit && lc && !t.premul && n >= 3 && n <= 8 && !dmask && (walk ? !tmxu_blocks_on(e, 1) : TMX_EXP != 0)) {      // (the block form of the walk stores none)
 		em.xp = prefix; em.first = emit->first; for (int m = 0; m < 12; m++) em.coef[m] = emit->coef[m];
+		st.emit = &em;
 	}
 	if (emit) e->u.prefix_for = em.xp ? (long long)emit->consumer : -1;      // which operation may start from the stored prefix (run_program_unique)
 	// the stage writes every slab of the update instance: its U,V slabs are its own from here on (what it shared is read through
 	// the pointers taken above), and whoever shared ITS slabs is dead
 	if (e->uvmap[iupd] != iupd) { e->uvmap[iupd] = iupd; e->n_uvshared--; }
-	if (aliased) u_adopt_spare(e, iupd);      // (src[], base and the U,V pointers were taken before: they still name the old slots)
-	int r = u_produce_and_average(e, iupd, TMX_K_H_EXPLICIT, [&](const KParams & p) {
-		if (n > 0) tmxk_h_explicit(e, p, xin, out, out, dt, 1, n, src, cf, premul, xin_uv, nullptr, srcuv, em.xp ? &em : nullptr, dmask);
-		else tmxk_h_explicit(e, p, xin, base, out, dt, 1, 0, nullptr, nullptr, 0, xin_uv, base_uv, nullptr, nullptr, dmask);
-	});
+	if (aliased) u_adopt_spare(e, iupd);      // (the stage's pointers were taken before: they still name the old slots)
+	int r = u_produce_and_average(e, iupd, TMX_K_H_EXPLICIT, [&](const KParams & p) { tmxk_h_explicit(e, p, st); });
 	e->u.dlive &= ~(1u << iupd);      // the instance is node-unique from here on
 	u_written(e, iupd);
 	if (r) return r;
-	if (lc) {
-		const double * dsrc[12]; double dcf[12];      // the surface slots live with the element-major slots (all terms: no prefix there)
-		int m2 = 1; dsrc[0] = inst(e, iupd); dcf[0] = lc[iupd];
-		for (int m = 0; m < nlc; m++) if (m != iupd && lc[m] != 0.0) { dsrc[m2] = inst(e, m); dcf[m2++] = lc[m]; }
-		return surface_lincomb(e, iupd, m2, dsrc, dcf, lc[iupd] != 0.0 ? 1 : 0);
-	}
-	return surface_copy(e, ibase, iupd);
+	return lc ? surface_lincomb(e, lc, nlc, iupd) : surface_copy(e, ibase, iupd);      // (all terms: no prefix there)
 }
 
 static int u_copy(tmx_engine * e, int a, int b, size_t doubles) {
@@ -846,12 +822,9 @@ static int u_hvis_core(tmx_engine * e, int iinit, int iupd, int iwork, double dt
 		return u_produce_and_average(e, iupd, TMX_K_HYPERVIS, [&](const KParams & p) {
 			tmxk_hypervis(e, p, uinst(e, iinit), uinst(e, iinit), uinst(e, iupd), -dt, -c.nu_scalar, c.nu_div, c.nu_vort, 0); });
 	}
-	const int scale = (c.reference_length != 0.0) ? 1 : 0;
 	if ((r = surface_copy(e, iinit, iupd)) || (r = surface_zero(e, iwork))) return r;
-	if ((r = u_produce_and_average(e, iwork, TMX_K_HYPERVIS, [&](const KParams & p) {
-		tmxk_hypervis(e, p, uinst(e, iinit), nullptr, uinst(e, iwork), 1.0, 1.0, 1.0, 1.0, 0); }))) return r;
-	return u_produce_and_average(e, iupd, TMX_K_HYPERVIS, [&](const KParams & p) {
-		tmxk_hypervis(e, p, uinst(e, iwork), uinst(e, iinit), uinst(e, iupd), -dt, c.nu_scalar, c.nu_div, c.nu_vort, scale); });
+	if ((r = u_produce_and_average(e, iwork, TMX_K_HYPERVIS, [&](const KParams & p) { hvis_laplacians(e, p, uinst(e, iinit), uinst(e, iwork)); }))) return r;
+	return u_produce_and_average(e, iupd, TMX_K_HYPERVIS, [&](const KParams & p) { hvis_apply(e, p, uinst(e, iwork), uinst(e, iinit), uinst(e, iupd), dt); });      // (no tracers on this layout)
 }
 
 static int run_program_unique(tmx_engine * e, const Program & p, Access ax) {
@@ -902,20 +875,14 @@ static int run_program_unique(tmx_engine * e, const Program & p, Access ax) {
 			if ((r = u_copy(e, o.a, o.b, e->u.ustride))) return r;
 			break;
 		case OP_LINCOMB: {
-			const double * src[12], * dsrc[12]; double cf[12];
 			if ((r = u_own_uv(e, o.a, o.lc[o.a] == 0.0))) return r;
 			for (int m = 0; m < o.nlc; m++) if (m != o.a && o.lc[m] != 0.0 && (r = u_own_uv(e, m))) return r;      // (whole-instance pass: one pointer per source)
-			int n = 1; src[0] = uinst(e, o.a); dsrc[0] = inst(e, o.a); cf[0] = o.lc[o.a];
-			for (int m = 0; m < o.nlc; m++) {
-				if (m == o.a || o.lc[m] == 0.0) continue;
-				REQUIRE(n < 12, TMX_ERR_UNSUPPORTED, "linear_combine_data: more than 11 source terms");
-				src[n] = uinst(e, m); dsrc[n] = inst(e, m); cf[n] = o.lc[m]; n++;
-			}
-			const int premul = o.lc[o.a] != 0.0 ? 1 : 0;
-			{ ProfScope ps(e, TMX_K_LINCOMB); tmxk_lincomb(e, e->u.ustride, uinst(e, o.a), n, src, cf, premul); }
+			StageTerms t;
+			REQUIRE(gather_terms(t, o.lc, o.nlc, o.a, 0u, WhereU{ e, 0u }), TMX_ERR_UNSUPPORTED, "linear_combine_data: more than 11 source terms");
+			{ ProfScope ps(e, TMX_K_LINCOMB); tmxk_lincomb(e, e->u.ustride, uinst(e, o.a), t); }
 			e->u.dlive &= ~(1u << o.a);
 			u_written(e, o.a);
-			if ((r = surface_lincomb(e, o.a, n, dsrc, cf, premul)) || (r = launch_check("lincomb"))) return r;
+			if ((r = surface_lincomb(e, o.lc, o.nlc, o.a)) || (r = launch_check("lincomb"))) return r;
 			break; }
 		case OP_VIMP: if ((r = u_vimp(e, o.a, o.b, o.coef, false))) return r; break;
 		case OP_DSS: if ((r = u_dss(e, o.a))) return r; break;
