@@ -425,8 +425,14 @@ enum {
 	TMX_INFO_EXPERIMENTS_BUILD,   /* 1: the experiments flavour of the library (archived experiments and cross-check kernels compiled in) */
 	TMX_INFO_MIXED_STEPS,         /* steps so far whose explicit stages read an element-major instance copy by copy beside node-unique ones ("unique_mixed") */
 	TMX_INFO_COLUMN_KERNEL,       /* the column-solve kernel of the last launch: 0 one wavefront per column group, 1 two-wavefront pair, 2 lane group, -1 none yet */
-	TMX_INFO_COLUMN_VARIANT       /* ... and which variant of it: pairs per workgroup | assembly wavefronts per pair << 4 | block rows of the LDS ring << 8 for the
+	TMX_INFO_COLUMN_VARIANT,      /* ... and which variant of it: pairs per workgroup | assembly wavefronts per pair << 4 | block rows of the LDS ring << 8 for the
 	                                 two-wavefront pair (the ring depth of the instantiation that ran: 2 or 3, 4 with two assembly wavefronts), 0 for the other kernels, -1 none yet */
+	TMX_INFO_STAGE_KERNEL,        /* the explicit-stage kernel of the last launch: 0 the level-parallel kernels, -1 none yet, otherwise the column-segment walk as
+	                                 segments per column (as handed to the kernel, after the clamp to levels / 2) | terms of the stage combination << 8 | flags << 16;
+	                                 flag bits: 0 the update instance enters its own combination, 1 element-major sources read copy by copy, 2 a later stage's prefix
+	                                 stored, 3 node-unique layout, 4 V.StepExplicit fused in, 5 uniform diffusion applied in the walk */
+	TMX_INFO_HYPERVIS_KERNEL      /* the kernel of the last hyperviscosity pass: 0 the level-parallel one, n > 0 the walk with n segments per column (after the clamp
+	                                 to (levels + 1) / 2), -1 none yet */
 };
 long long tmx_info(tmx_engine * e, int what);
 

@@ -508,6 +508,7 @@ void tmxk_h_explicit(tmx_engine * e, const KParams & p, const StageIO & st) {
 	const EmitTerms * emit = st.emit;
 	// the column-segment walk (tmx_k_hwalk.hip) does the whole stage, W of every interface included (node-unique layout: with the vertical part fused in)
 	if (tmxk_h_walk_ok(e, p, fuse_v, nterms, emit && emit->xp)) { tmxk_h_walk(e, p, st); return; }
+	e->stage_kernel_launched = 0;      // (tmx_info(TMX_INFO_STAGE_KERNEL): the level-parallel kernels below)
 	// base of the update: a plain instance (nterms == 0) or a linear combination evaluated in the kernels
 	LinTerms xbase;
 	UvTerms uvt;
@@ -1051,6 +1052,7 @@ void tmxk_hypervis(tmx_engine * e, const KParams & p, const double * xsrc, const
 	dim3 blk(64, 4);
 	DssPull d = { (const int4 *)e->d_colref, (const double *)e->d_xmat, (const double *)e->d_ghost, (const int *)e->d_ghost_base, (const int *)e->d_ghost_stride };
 	if (tmxk_hv_walk_ok(e, p)) { tmxk_hv_walk(e, p, xsrc, xbase, xout, dt, nu_s, nu_d, nu_v, scale); return; }      // node-unique layout: the pass as a walk (tmx_k_hwalk.hip)
+	e->hypervis_kernel_launched = 0;      // (tmx_info(TMX_INFO_HYPERVIS_KERNEL): k_hypervis below)
 	if (p.t_ucol) {      // node-unique layout (tmxu_params)
 		KParams q = p; q.u_ntiles = ntiles;
 		const bool blocks = tmxu_blocks_on(e, 2);      // a workgroup = a block of the thread order at one level: its seams are averaged in the kernel

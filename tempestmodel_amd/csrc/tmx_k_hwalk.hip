@@ -679,11 +679,16 @@ void tmxk_h_walk(tmx_engine * e, const KParams & p, const StageIO & st) {
 	// (three wavefronts per SIMD -- at most 168 registers -- for the plain stage and the two-term combination without a coefficient of its own)
 	const int nseg = tmxk_h_walk_segments(e, p, ntile, nterms, ((!p.t_ucol && tmxk_h_walk_fuses_udiff(e, p, fuse_v, nterms)) || (nterms == 2 && premul)) ? 2 : 0);
 	KParams q = p; q.u_ntiles = ntile;
+	// (tmx_info(TMX_INFO_STAGE_KERNEL): the segments handed to the kernel, the terms and the instantiation's flags -- PM, DM, EM, UQ, FV, UD)
+	auto launched = [&](bool dm, bool em, bool uq, bool ud) {
+		e->stage_kernel_launched = nseg | nterms << 8 | ((nterms > 0 && premul ? 1 : 0) | (dm ? 2 : 0) | (em ? 4 : 0) | (uq ? 8 : 0) | (fuse_v ? 16 : 0) | (ud ? 32 : 0)) << 16;
+	};
 	if (!p.t_ucol) {
 		// element-major layout: 2-D launch (tile list or all tiles) x segments
 		EmitTerms em1; em1.xp = nullptr; em1.first = -1; for (int m = 0; m < 12; m++) em1.coef[m] = 0.0;
 		const dim3 grd(ntile, nseg), blk(64);
 		const bool udf = tmxk_h_walk_fuses_udiff(e, p, fuse_v, nterms);
+		launched(false, false, false, udf);
 		// (fuse_v with uniform diffusion: the vertical diffusion of U, V rides along where k_v_explicit_slide would apply it -- the fully explicit mode)
 		const UdiffArgs ud0 = { nullptr, 0.0, 0.0, nullptr, 0.0, 0 }, ud1 = { (const double *)e->d_ref, e->cfg.uniform_diffusion_scalar, e->cfg.uniform_diffusion_vector,
 			udf ? ref_diffusion_terms(e, p) : nullptr, e->cfg.uniform_diffusion_vector / (e->cfg.ztop * e->cfg.ztop), (e->fully_explicit && !e->opt_udv_separate) ? 1 : 0 };
@@ -707,6 +712,7 @@ void tmxk_h_walk(tmx_engine * e, const KParams & p, const StageIO & st) {
 	// (the prefix of a later stage's combination: no own coefficient, three to eight terms, node-unique sources, wavefront-level kernel)
 	const bool emit_ok = emit && emit->xp && !premul && !dmask && !blocks && nterms >= 3 && nterms <= 8;
 	const EmitTerms em = emit_ok ? *emit : em0;
+	launched(dmask != 0, emit_ok, true, false);
 	dispatch_terms_pm<8>(nterms, premul, [&](auto nt, auto pm) {
 		auto launch = [&](auto dm) {
 			constexpr int NT_ = decltype(nt)::value; constexpr bool PM_ = decltype(pm)::value, DM_ = decltype(dm)::value;
@@ -859,6 +865,7 @@ void tmxk_hv_walk(tmx_engine * e, const KParams & p, const double * xsrc, const 
 	KParams pl = p; pl.L = p.L + 1;      // (segments over the L + 1 levels)
 	const int nseg = tmxk_h_walk_segments(e, pl, ntile, 0, 4);      // (128 registers: four wavefronts per SIMD; ne30: 3 segments = 4 050 wavefronts in 4 096 slots)
 	e->u.slots_by_blocks = false;
+	e->hypervis_kernel_launched = nseg;      // (tmx_info(TMX_INFO_HYPERVIS_KERNEL))
 	const dim3 grd = wg_grid(true, q, ntile, nseg);
 	if (xbase) hipLaunchKernelGGL(k_hv_walk<true>, grd, dim3(64), 0, e->stream, q, xsrc, xbase, xout, dt, nu_s, nu_d, nu_v, scale, nseg);
 	else hipLaunchKernelGGL(k_hv_walk<false>, grd, dim3(64), 0, e->stream, q, xsrc, xbase, xout, dt, nu_s, nu_d, nu_v, scale, nseg);
