@@ -431,8 +431,12 @@ enum {
 	                                 segments per column (as handed to the kernel, after the clamp to levels / 2) | terms of the stage combination << 8 | flags << 16;
 	                                 flag bits: 0 the update instance enters its own combination, 1 element-major sources read copy by copy, 2 a later stage's prefix
 	                                 stored, 3 node-unique layout, 4 V.StepExplicit fused in, 5 uniform diffusion applied in the walk */
-	TMX_INFO_HYPERVIS_KERNEL      /* the kernel of the last hyperviscosity pass: 0 the level-parallel one, n > 0 the walk with n segments per column (after the clamp
+	TMX_INFO_HYPERVIS_KERNEL,     /* the kernel of the last hyperviscosity pass: 0 the level-parallel one, n > 0 the walk with n segments per column (after the clamp
 	                                 to (levels + 1) / 2), -1 none yet */
+	TMX_INFO_PHYSICS_KERNEL       /* the kernel of the last tmx_physics_kessler / tmx_physics_dcmip2016 launch, -1 none yet, otherwise family | pbl << 2 | prec << 3 |
+	                                 n << 4; family (bits 0-1): 1 k_kessler (one lane per column; n = 0), 2 k_kessler_tile (n = kt, the wavefronts the levels
+	                                 of a column are dealt out to), 3 k_dcmip (pbl, prec the instantiation's; n = the bytes of dynamic LDS it was launched
+	                                 with, 0 the variant with its Thomas coefficients in HBM, whatever "dcmip_lds" asked for); pbl = prec = 0 for Kessler */
 };
 long long tmx_info(tmx_engine * e, int what);
 

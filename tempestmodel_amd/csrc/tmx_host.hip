@@ -986,6 +986,7 @@ extern "C" long long tmx_info(tmx_engine * e, int what) {
 		case TMX_INFO_COLUMN_VARIANT: return e->vi_variant_launched;
 		case TMX_INFO_STAGE_KERNEL: return e->stage_kernel_launched;
 		case TMX_INFO_HYPERVIS_KERNEL: return e->hypervis_kernel_launched;
+		case TMX_INFO_PHYSICS_KERNEL: return e->physics_kernel_launched;
 		case TMX_INFO_COMM_RANKS: {      // what RCCL itself reports for the communicator (0: no communicator)
 			int n = 0;
 			if (e->comm && g_nccl.CommCount && g_nccl.CommCount(e->comm, &n) == 0) return n;

@@ -287,6 +287,7 @@ struct tmx_engine {
 	int vi_kernel_launched = -1;             // the column-solve kernel of the last launch: 0 one wavefront per column group, 1 pair (assembly || elimination), 2 lane group; -1 none yet
 	int vi_variant_launched = -1;            // ... and its variant: pairs per workgroup | assembly wavefronts per pair << 4 | block rows of the LDS ring << 8 (pair kernel), 0 (the others); -1 none yet
 	int stage_kernel_launched = -1;          // the explicit-stage kernel of the last launch (tmx_info(TMX_INFO_STAGE_KERNEL)): 0 level-parallel, walk: segments | terms << 8 | flags << 16; -1 none yet
+	long long physics_kernel_launched = -1;  // the kernel of the last Kessler / DCMIP2016 launch (TMX_INFO_PHYSICS_KERNEL): family | pbl << 2 | prec << 3 | n << 4 (kt or LDS bytes); -1 none yet
 	int hypervis_kernel_launched = -1;       // the kernel of the last hyperviscosity pass (TMX_INFO_HYPERVIS_KERNEL): 0 level-parallel, n: the walk with n segments; -1 none yet
 	int vi_cpw = 64, vi_stream_cols = 0;     // columns per wavefront of k_vi_pair (TMX_VI_CPW; auto: fill every SIMD evenly), stream columns allocated
 	int p2p_timeout_s = 600;                 // peer-to-peer halo: how long a neighbour's message may take (TMX_P2P_TIMEOUT_S; 0 = for ever)

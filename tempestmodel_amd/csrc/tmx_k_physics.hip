@@ -382,10 +382,12 @@ void tmxk_kessler(tmx_engine * e, const KParams & p, double * x, double dt) {
 	const int kt = (p.L + KES_NO - 1) / KES_NO;
 	const size_t lds = (size_t)p.L * 64 * (2 * sizeof(double) + 2 * sizeof(float)) + 64 * sizeof(double);
 	if (kt <= 8 && !e->opt_kessler_column) {
+		e->physics_kernel_launched = 2 | (long long)kt << 4;      // (tmx_info(TMX_INFO_PHYSICS_KERNEL): k_kessler_tile and its kt)
 		if (lds > 48 * 1024) hipFuncSetAttribute((const void *)k_kessler_tile<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 		hipLaunchKernelGGL(k_kessler_tile<512>, dim3((p.ncol + 63) / 64), dim3(64, kt), lds, e->stream, p, x, (const double *)e->d_zlev, e->d_prect, dt, gamma, pscal);
 		return;
 	}
+	e->physics_kernel_launched = 1;      // (k_kessler)
 	hipLaunchKernelGGL(k_kessler, dim3((p.ncol + 255) / 256), dim3(256), 0, e->stream, p, x, (const double *)e->d_zlev, e->d_kes, e->d_prect, dt, gamma, pscal);
 }
 
@@ -634,6 +636,8 @@ size_t tmxk_dcmip_lds_bytes(int L) {
 template <int PBL, int PREC>
 static void launch_dcmip(tmx_engine * e, const KParams & p, double * x, double dt, int test, double gamma, double pscal, double kappa, double a, bool lds) {
 	const dim3 grid((p.ncol + 63) / 64), blk(64);
+	// (tmx_info(TMX_INFO_PHYSICS_KERNEL): the instantiation launched below and the dynamic LDS it gets, 0 for the HBM variant)
+	e->physics_kernel_launched = 3 | PBL << 2 | PREC << 3 | (long long)(lds ? tmxk_dcmip_lds_bytes(p.L) : 0) << 4;
 	if (lds) {
 		const size_t b = tmxk_dcmip_lds_bytes(p.L);
 		if (b > 48 * 1024) hipFuncSetAttribute((const void *)k_dcmip<PBL, PREC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);

@@ -18,6 +18,16 @@ TerminatorPhysics.cpp (g++ at oracle/Makefile's REFFLAGS) and Fortran halves (am
 Both cases run with ztop = 4.5 km in 6 levels on the ne2 grid of 6 patches (the smallest grid with a GLL node at the polar panel
 centres).
 States after a call are stored as the bitwise XOR with the state they started from (tests/dcmip_common.py: decode_after).
+
+tests/dcmip_common.py: SLIM lists further shapes (tests/test_gpu_dcmip_levels.py; what each reaches: DESIGN.md section 2).  Each gets ONE slim file per
+case, dcmip_<case>_slim_ne<ne>_L<L>_z<ztop>_dt<dt>_p6.npz, holding only what the physics reads and what the tests compare: cfg/,
+phys/, per patch lat, a_nodes, b_nodes and the level and interface height columns, the MOIST starting state, its five calls as XOR
+against it, PRECT of each call and the branch counters.  The metric geometry, the operators and the stock and warm states are left
+out: the physics reads none of the metric, and the tests build the engine's grid object with golden_util.make_grid and upload
+everything else from the file (tests/dcmip_common.py: slim_setup).
+
+A file whose arrays have not changed is left as it is on disk (a .npz carries the time it was written: byte-identical fixtures
+stay byte-identical).
 """
 import os
 import shutil
@@ -29,9 +39,11 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, HERE)
 import tmxd  # noqa: E402
+import dcmip_common as dc  # noqa: E402
 from make_golden import compact_states, flat_geometry, save  # noqa: E402
 
 REF = "/root/reference"
@@ -43,6 +55,7 @@ ENV = dict(os.environ, MKL_THREADING_LAYER="SEQUENTIAL")
 # ztop 4.5 km in 6 levels of 750 m: interface 1 lies inside the Bryan boundary layer (0 < zi < zpbltop, a non-zero diffusivity),
 # the others above it, and presi crosses pbltop a few interfaces up, so both sides of both boundary-layer tests act
 NE, L, DT, ZTOP = 2, 6, 300.0, 4500.0
+# the slim fixtures' shapes, id -> (ne, L, ztop, dt, cases), and their file names: tests/dcmip_common.py (SLIM, slim_name), which the tests read too
 COMBOS = ["t%d_pbl%d_prec%d" % (2, pb, pr) for pb in (0, 1) for pr in (0, 1)]
 
 
@@ -115,12 +128,59 @@ def branch_counts(d, tag, test):
     return c
 
 
-def percall(exe, tmp, case, name):
+def save_if_changed(name, rec):
+    """make_golden.save, unless the file on disk already holds exactly these arrays (names, types, shapes, bits)."""
+    path = os.path.join(HERE, name)
+    if os.path.exists(path):
+        with np.load(path) as z:
+            old = {k.replace("__", "/"): z[k] for k in z.files}
+        if set(old) == set(rec) and all(old[k].dtype == np.asarray(rec[k]).dtype and old[k].shape == np.asarray(rec[k]).shape
+                                        and old[k].tobytes() == np.ascontiguousarray(rec[k]).tobytes() for k in rec):
+            print(name, "unchanged, %.2f MB" % (os.path.getsize(path) / 1e6))
+            return
+    save(name, rec)
+
+
+PART_LIMIT = 1 << 20      # no committed file is larger than 1 MiB
+
+
+def save_slim(name, rec):
+    """One slim fixture, cut where it is larger than PART_LIMIT: <name> holds everything but the calls' states, and as many
+    calls' XOR arrays as fit; the following calls go to <name less .npz>.part1.npz, ... (tests/dcmip_common.py: load_slim joins
+    them).  Parts left over from an earlier, longer cut are removed."""
+    calls = sorted({k.split("/")[1] for k in rec if k.startswith("xor/")})
+    groups = [{k: v for k, v in rec.items() if not k.startswith("xor/")}] + [{k: v for k, v in rec.items() if k.startswith("xor/%s/" % c)} for c in calls]
+    probe = os.path.join(tempfile.gettempdir(), "dcmip_probe_%d.npz" % os.getpid())
+
+    def size(r):
+        np.savez_compressed(probe, **{k.replace("/", "__"): v for k, v in r.items()})
+        n = os.path.getsize(probe); os.remove(probe)
+        return n
+    parts, cur = [], groups[0]
+    for g in groups[1:]:
+        both = dict(cur); both.update(g)
+        if size(both) <= PART_LIMIT:
+            cur = both
+        else:
+            parts.append(cur); cur = g
+    parts.append(cur)
+    stem = name[:-len(".npz")]
+    names = [name] + ["%s.part%d.npz" % (stem, i) for i in range(1, len(parts))]
+    for stale in glob.glob(os.path.join(HERE, stem + ".part*.npz")):
+        if os.path.basename(stale) not in names:
+            os.remove(stale)
+    for n, r in zip(names, parts):
+        save_if_changed(n, r)
+        assert os.path.getsize(os.path.join(HERE, n)) <= PART_LIMIT, n
+
+
+def percall(exe, tmp, case, name, ne=NE, nlev=L, ztop=ZTOP, dt=DT, slim=False):
     test = 2 if case == "tc" else 1
-    d = run(exe, tmp, ["--case", case, "--mode", "percall", "--ne", str(NE), "--levels", str(L), "--dt", str(DT),
-                       "--ztop", str(ZTOP), "--warm", "2", "--pbl", "1", "--prec", "1", "--moisten", "1.5"])
-    rec = {k: v for k, v in d.items() if k.startswith(("cfg/", "phys/", "grid/"))}
-    rec.update(flat_geometry(d))
+    d = run(exe, tmp, ["--case", case, "--mode", "percall", "--ne", str(ne), "--levels", str(nlev), "--dt", str(dt),
+                       "--ztop", str(ztop), "--warm", "2", "--pbl", "1", "--prec", "1", "--moisten", "1.5"])
+    rec = {k: v for k, v in d.items() if k.startswith(("cfg/", "phys/") if slim else ("cfg/", "phys/", "grid/"))}
+    if not slim:
+        rec.update(flat_geometry(d))
     for p in range(6):
         for nm in ("a_nodes", "b_nodes", "lat"):
             rec["p%d/%s" % (p, nm)] = d["p%d/%s" % (p, nm)]
@@ -150,15 +210,21 @@ def percall(exe, tmp, case, name):
         if k.startswith("prect/"):
             rec[k] = v
     print(name)
-    for tag in ("stock", "warm", "moist"):
+    for tag in ("moist",) if slim else ("stock", "warm", "moist"):
         cnt = branch_counts(d, tag, test)
         for k, v in cnt.items():
             rec["branches/%s/%s" % (tag, k)] = np.array([v], dtype=np.int64)
         print("  %-6s" % tag, " ".join("%s=%d" % kv for kv in cnt.items()))
     # the moistened state's calls in a file of their own (tests/dcmip_common.py: load_case joins the two)
     moist = {k: v for k, v in rec.items() if k.split("/")[1].startswith("moist")}
-    save(name, {k: v for k, v in rec.items() if k not in moist})
-    save(name.replace("_ne", "_moist_ne", 1), moist)
+    if slim:
+        # one file: what the physics reads (cfg, phys, lat, node angles, height columns) and the moist state's calls
+        keep = {k: v for k, v in rec.items() if k in moist or k.startswith(("cfg/", "phys/")) or k.split("/")[0][0] == "p" and k[1].isdigit()}
+        assert all(np.all(np.isfinite(v)) for k, v in keep.items() if v.dtype == np.float64), name
+        save_slim(name, keep)
+        return cs
+    save_if_changed(name, {k: v for k, v in rec.items() if k not in moist})
+    save_if_changed(name.replace("_ne", "_moist_ne", 1), moist)
     return cs
 
 
@@ -179,7 +245,7 @@ def steps(exe, tmp, name, warm):
         for p in range(6):
             rec["prect/pbl%d_prec%d_steps/p%d" % (pb, pr, p)] = d["prect/steps/p%d" % p]
         rec["cfg/dt"] = d["cfg/dt"]
-    save(name, rec)
+    save_if_changed(name, rec)
 
 
 def main():
@@ -188,9 +254,15 @@ def main():
     tmp = tempfile.mkdtemp()
     try:
         exe = build(tmp)
-        tc = percall(exe, tmp, "tc", "dcmip_tc_ne%d_L%d_p6.npz" % (NE, L))
-        percall(exe, tmp, "bw", "dcmip_bw_ne%d_L%d_p6.npz" % (NE, L))
-        steps(exe, tmp, "dcmip_tc_steps_ne%d_L%d_p6.npz" % (NE, L), tc)
+        only = sys.argv[1:]      # ids of dcmip_common.SLIM: those slim files alone; none: every file
+        if not only:
+            tc = percall(exe, tmp, "tc", "dcmip_tc_ne%d_L%d_p6.npz" % (NE, L))
+            percall(exe, tmp, "bw", "dcmip_bw_ne%d_L%d_p6.npz" % (NE, L))
+            steps(exe, tmp, "dcmip_tc_steps_ne%d_L%d_p6.npz" % (NE, L), tc)
+        for sid, (ne, nlev, ztop, dt, cases) in dc.SLIM.items():
+            for case in cases:
+                if not only or sid in only:
+                    percall(exe, tmp, case, dc.slim_name(sid, case) + ".npz", ne, nlev, float(ztop), float(dt), slim=True)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 

@@ -112,3 +112,110 @@ def test_moist_baroclinic_wave_leaves_the_chemistry_tracers_alone():
         tr = d["state/%s/p0/tracers" % start]
         assert tr.shape[0] == 5 and np.any(tr[3:] != 0.0)
         assert d["xor/%s_t1_pbl0_prec0/p0/tracers" % start].shape[0] == 3
+
+
+# which branch counters each slim file leaves at zero (everything else is > 0); asserted exactly below
+SLIM_MISSES = {
+    ("A", "tc"): set(),
+    ("B", "tc"): {"wind_above_20_columns"},
+    ("B", "bw"): {"wind_below_20_columns"},
+    ("Bp", "tc"): {"wind_above_20_columns"},
+    ("C", "tc"): {"wind_above_20_columns"},
+    ("D", "tc"): {"wind_above_20_columns", "zi_inside_bryan_pbl_interfaces"},
+    ("D", "bw"): {"wind_below_20_columns", "zi_inside_bryan_pbl_interfaces"},
+    ("E", "tc"): {"wind_above_20_columns", "zi_le_zpbltop_interfaces", "zi_inside_bryan_pbl_interfaces"},
+}
+
+
+@pytest.mark.parametrize("sid,case", dc.SLIM_FILES, ids=dc.SLIM_IDS)
+def test_slim_fixtures_are_worth_pinning(sid, case):
+    """The slim fixtures at the further shapes (dcmip_common.SLIM): every array finite; a column count that is no multiple of 64
+    (864 = 13.5 workgroups at ne3, 96 = 1.5 at ne1); every recorded call differs from the starting state on every patch; the four
+    (pbl, prec) results differ pairwise and test 3 differs from the file's own test with the same options; the baroclinic wave's
+    tracers 3 and 4 are not all zero.
+
+    A alone reaches both sides of every branch.  The ne1 grids do not, one file at a time -- 96 columns of one case lie on one side
+    of 20 m/s: the tropical cyclone has no column above it, the baroclinic wave none below, so B and D reach both sides only with
+    their two cases together (asserted), and B', C and E, which have the tropical cyclone alone, run the wind < 20 m/s side only.
+    D (30 levels in 30 km, production's) has its lowest interior interface at 1 km: none lies strictly inside the Bryan layer, which
+    is the branch mix production runs.  E (4 levels of 1125 m; the reference's column solve refuses 3) has no interior interface at
+    or below 1 km either.  SLIM_MISSES holds exactly this, and is asserted as an equality."""
+    d = dc.load_slim(sid, case)
+    ne, L, ztop, dt, _ = dc.SLIM[sid]
+    assert (int(d["cfg/ne"][0]), int(d["cfg/levels"][0]), float(d["cfg/ztop"][0]), float(d["cfg/dt"][0])) == (ne, L, float(ztop), float(dt))
+    for k, v in d.items():
+        if v.dtype == np.float64:
+            assert np.all(np.isfinite(v)), k
+    ncol = sum(d["state/moist/p%d/node" % p].shape[1] * d["state/moist/p%d/node" % p].shape[2] for p in range(6))
+    assert ncol == 96 * ne * ne and ncol % 64 != 0, ncol
+    assert not any(k.startswith(("state/stock", "state/warm", "op/", "grid/", "halo_trans/")) or "metric" in k or "jacobian" in k for k in d)
+    calls = [dc.call_key(*c) for c in dc.slim_calls(d)]
+    test = dc.slim_test(d)
+    assert test == (2 if case == "tc" else 1)
+    for p in range(6):
+        res = {}
+        for call in calls:
+            assert np.any(d["xor/%s/p%d/node" % (call, p)] != 0) and np.any(d["xor/%s/p%d/tracers" % (call, p)] != 0), (call, p)
+            res[call] = np.concatenate([dc.decode_after(d, "moist", call, p, "node").ravel(), dc.decode_after(d, "moist", call, p, "tracers").ravel()])
+        four = calls[:4]
+        for i in range(4):
+            for j in range(i + 1, 4):
+                assert not np.array_equal(res[four[i]], res[four[j]]), (four[i], four[j], p)
+        assert not np.array_equal(res["moist_t3_pbl0_prec0"], res[dc.call_key(test, 0, 0)]), p
+        if case == "bw":
+            tr = d["state/moist/p%d/tracers" % p]
+            assert tr.shape[0] == 5 and np.any(tr[3] != 0.0) and np.any(tr[4] != 0.0), p
+    for pr_ in (0, 1):
+        assert sum(float(np.sum(d["prect/%s/p%d" % (dc.call_key(test, 0, pr_), p)])) for p in range(6)) > 0.0
+    zero = {k.split("/")[-1] for k, v in d.items() if k.startswith("branches/moist/") and int(v[0]) == 0}
+    assert len([k for k in d if k.startswith("branches/moist/")]) == 10
+    assert zero == SLIM_MISSES[(sid, case)], zero
+
+
+def test_slim_ne1_cases_reach_both_wind_branches_jointly():
+    """B and D: the tropical cyclone and the baroclinic wave together leave no counter at zero but D's `inside the Bryan layer`."""
+    for sid, allowed in (("B", set()), ("D", {"zi_inside_bryan_pbl_interfaces"})):
+        assert SLIM_MISSES[(sid, "tc")] & SLIM_MISSES[(sid, "bw")] == allowed, sid
+    assert not SLIM_MISSES[("A", "tc")]
+
+
+def test_checkerboard_partners_differ_at_every_column():
+    """B and B' (same grid, level count and dt; tops of 12 and 4.5 km) share latitude and node angles and differ in every level and
+    interface height above the ground and, at every column, in the starting state and in every recorded result: a checkerboard of the
+    two (tests/test_gpu_dcmip_levels.py) puts different heights and different states into neighbouring lanes."""
+    b, bp = dc.load_slim("B"), dc.load_slim("Bp")
+    assert float(b["cfg/dt"][0]) == float(bp["cfg/dt"][0])
+    for p in range(6):
+        for nm in ("lat", "a_nodes", "b_nodes"):
+            assert np.array_equal(b["p%d/%s" % (p, nm)], bp["p%d/%s" % (p, nm)]), (p, nm)
+        assert np.all(b["p%d/dcmip_z_levels" % p] != bp["p%d/dcmip_z_levels" % p])
+        assert np.all(b["p%d/dcmip_z_interfaces" % p][1:] != bp["p%d/dcmip_z_interfaces" % p][1:])
+        for what in ("node", "tracers"):
+            x, y = b["state/moist/p%d/%s" % (p, what)], bp["state/moist/p%d/%s" % (p, what)]
+            assert np.all(np.any(x != y, axis=(0, 3))), (p, what)
+            for call in (dc.call_key(*c) for c in dc.slim_calls(b)):
+                x, y = dc.decode_after(b, "moist", call, p, what), dc.decode_after(bp, "moist", call, p, what)
+                assert np.all(np.any(x != y, axis=(0, 3))), (p, what, call)
+
+
+def test_kessler_subcycles_differ_inside_the_first_wavefront_of_A():
+    """levels_common.kessler_subcycles (an estimate of the rain loop's sub-cycle count, float64 throughout) on A's moist state with A's
+    heights and dt: the 64 columns of the first wavefront of k_dcmip hold more than one count, so lanes leave the loop at different
+    trips.  (k_dcmip's Kessler works on the state the subroutine derives -- dry density, the clamped mixing ratios --, the same
+    quantities the estimate forms.)"""
+    import levels_common as lc
+    d = dc.load_slim("A")
+    g = dc.slim_grid(d)
+    states, tracers, saved = gu.expand_compact(d, "moist", g), gu.expand_compact_tracers(d, "moist", g), []
+    for P in g.patches:
+        saved.append(P.geom["z_levels"])
+        P.geom["z_levels"] = dc.heights(d, P)[0]
+    try:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            n = lc.kessler_subcycles(g, states, tracers, float(d["cfg/dt"][0]))
+    finally:
+        for P, z in zip(g.patches, saved):
+            P.geom["z_levels"] = z
+    first = sorted(set(int(v) for v in n[:64]))
+    print("A: rain sub-cycle counts in the first wavefront %s, over all %d columns %s" % (first, n.size, sorted(set(int(v) for v in n))))
+    assert len(first) > 1, first

@@ -31,21 +31,26 @@ def _upload(e, d, g, tag):
 
 
 def _check_call(e, d, g, start, call):
-    """The device state after a call against the fixture, == 0.0 everywhere (W and tracers 3+ against the starting state)."""
+    """The device state after a call against the fixture, == 0.0 everywhere (W and tracers 3+ against the starting state).  A value
+    that is not finite comes back as it is and fails the caller's `== 0.0`: Python's max(0.0, nan) is 0.0, which would let a NaN result pass."""
     got, gt = e.download_state(0), e.download_tracers(0)
     prect = e.download_precipitation(reset=True)
     worst = 0.0
+
+    def fold(worst, diff):
+        m = float(np.max(diff))
+        return m if not np.isfinite(m) or m > worst else worst      # (inf stays: nothing compares greater)
     for P in g.patches:
         p = P.index
         n, w = got[p]
         ref_n = dc.decode_after(d, start, call, p, "node")
-        worst = max(worst, float(np.max(np.abs(n[[0, 1, 2, 4], 1:-1, 1:-1] - ref_n))))
-        worst = max(worst, float(np.max(np.abs(w[3, 1:-1, 1:-1] - d["state/%s/p%d/redge" % (start, p)]))))
+        worst = fold(worst, np.abs(n[[0, 1, 2, 4], 1:-1, 1:-1] - ref_n))
+        worst = fold(worst, np.abs(w[3, 1:-1, 1:-1] - d["state/%s/p%d/redge" % (start, p)]))
         t = gt[p][:, 1:-1, 1:-1]
-        worst = max(worst, float(np.max(np.abs(t[:3] - dc.decode_after(d, start, call, p, "tracers")))))
+        worst = fold(worst, np.abs(t[:3] - dc.decode_after(d, start, call, p, "tracers")))
         if t.shape[0] > 3:
-            worst = max(worst, float(np.max(np.abs(t[3:] - d["state/%s/p%d/tracers" % (start, p)][3:]))))
-        worst = max(worst, float(np.max(np.abs(prect[p][1:-1, 1:-1] - d["prect/%s/p%d" % (call, p)][1:-1, 1:-1]))))
+            worst = fold(worst, np.abs(t[3:] - d["state/%s/p%d/tracers" % (start, p)][3:]))
+        worst = fold(worst, np.abs(prect[p][1:-1, 1:-1] - d["prect/%s/p%d" % (call, p)][1:-1, 1:-1]))
     return worst
 
 

@@ -12,7 +12,7 @@ from parity_common import EXACT, UDIFF
 
 pytestmark = pytest.mark.gpu
 
-INFO_UNIQUE_INSTANCES, INFO_UNIQUE_CONVERSIONS = 13, 14      # tmx_info (include/tempest_mi355x.h)
+INFO_UNIQUE_INSTANCES, INFO_UNIQUE_CONVERSIONS, INFO_PHYSICS_KERNEL = 13, 14, 24      # tmx_info (include/tempest_mi355x.h)
 
 
 @pytest.mark.parametrize("L", lc.KESSLER_LEVELS)
@@ -33,8 +33,9 @@ def test_kessler_kernels_vs_oracle(L):
 
     864 columns leave the last workgroup of k_kessler_tile half filled (32 lanes repeat the last column and store nothing) and the
     last one of k_kessler with 96 of 256 lanes.  For L <= 40 the same calls with the option kessler_column = 1 give the same bits
-    from both kernels, raw (halo included: neither kernel writes there).  Neither tmx_info nor tmx_profile_get tells which Kessler
-    kernel ran (both are timed as TMX_K_LINCOMB): the dispatch is read from tmxk_kessler, kt <= 8 and no option, not asserted.
+    from both kernels, raw (halo included: neither kernel writes there).  tmx_info(TMX_INFO_PHYSICS_KERNEL) tells which Kessler
+    kernel ran and is asserted after every pair of calls: k_kessler_tile with kt = ceil(L / 5) up to L = 40 (2 | kt << 4), k_kessler (1)
+    at 41 and 60 and under kessler_column = 1.
 
     Shown to bite in a scratch build: with `if (k < L - 1)` -> `if (k < L)` in front of the sedimentation term of k_kessler_tile (the
     top level then takes the two-sided form with zeros from above; in bounds) every L <= 40 fails the comparison with the oracle at
@@ -60,6 +61,8 @@ def test_kessler_kernels_vs_oracle(L):
             for e in engines:
                 e.upload_state(0, st); e.upload_tracers(0, tr)
                 e.kessler(0, dt); e.kessler(0, dt); e.sync()
+                kt = {3: 1, 5: 1, 6: 2, 31: 7, 32: 7, 37: 8, 40: 8, 41: 0, 60: 0}[L]      # 0: the column kernel
+                assert e.info(INFO_PHYSICS_KERNEL) == (1 if e.options or not kt else 2 | kt << 4), (L, e.options, e.info(INFO_PHYSICS_KERNEL))
                 gs, gt, pr = e.download_state(0), e.download_tracers(0), e.download_precipitation(reset=True)
                 errs, terrs = gu.prognostic_errors(gs, o.get_state(0)), gu.tracer_errors(gt, o.get_tracers(0))
                 print("Kessler L %d dt %g %s: vs oracle %s %s" % (L, dt, e.options or "default", errs, terrs))
