@@ -543,6 +543,10 @@ int tmx_debug_program_rayleigh(int scheme, int first_step, int last_step);
  * stores (node-unique layout, option "unique_prefix").  Returns their number; pairs[2 k], pairs[2 k + 1] (k < cap): operation
  * index of the producing and of the consuming stage; terms[k]: source instances the consuming stage no longer reads. */
 int tmx_debug_program_prefix(int scheme, int first_step, int last_step, int * pairs, int * terms, int cap);
+/* Host logic of the column-walking vertical kernels (options "vx_walk", "vt_explicit_walk", "vite_walk"), no device: the number of segments a
+ * column of `rows` rows is walked in on a grid of `ntiles` 64-column tiles.  option -n = n segments; -1000 = segments in pairs until the grid
+ * has target_wavefronts wavefronts (4096 for vx_walk, 2048 for the other two), at least five rows each.  Always 1 .. rows. */
+int tmx_debug_walk_segments(int option, int ntiles, int rows, int target_wavefronts);
 /* Diagnostic builds of the library (-DTMX_H_TIMING) only, zeros otherwise: shader cycles per wavefront of the fused explicit kernel by
  * phase, out[16 instantiations (combination terms)][7 phases + wavefront count] (tools/h_timing.py); the read clears the counters. */
 int tmx_debug_h_timing(tmx_engine * e, unsigned long long * out);

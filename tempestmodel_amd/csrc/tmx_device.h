@@ -311,6 +311,86 @@ __device__ __forceinline__ double dss_combine(double w0, double w1, double w2, d
 }
 
 
+// Coefficient (row k, offset off) of operator `op` in a copy of the operator tables: p.ops in global memory (OPC) or staged in LDS (OPCL)
+__device__ __forceinline__ double op_coef(const double * ops, int L, int op, int k, int off) { return ops[((op * (L + 1)) + k) * TMX_OPW + (off + 2)]; }
+#define OPCL(op, k, off) opsl[(((op) * (p.L + 1)) + (k)) * TMX_OPW + ((off) + 2)]
+
+// The four-node stencil row of an operator that takes node values to interface m (InterpolateNodeToREdge, DifferentiateNodeToREdge:
+// LinearColumnOperatorFEM.cpp:1863-1888): nodes m - 2 .. m + 1 in ascending order, the ones outside the column skipped, accumulated
+// from 0.0.  val(off) = the value on level m + off, wherever the caller keeps it (a register window: a compile-time index; LDS; global memory).
+template <class V>
+__device__ __forceinline__ double edge_sum(const double * ops, int L, int op, int m, V val) {
+	double s = 0.0;
+#pragma unroll
+	for (int off = -2; off <= 1; off++) {
+		const int l = m + off;
+		if (l < 0 || l >= L) continue;
+		s += op_coef(ops, L, op, m, off) * val(off);
+	}
+	return s;
+}
+
+// First-order upwind penalty of level k (LinearColumnDiscPenaltyFEM::Apply; VerticalDynamicsFEM.cpp:984-1023, :4153-4181) added to
+// `acc`: x(d) = the column's value on level k + d (read only where it exists), w_lo / w_hi = the weights of the interfaces k and k + 1.
+// U,V: acc = the value being updated, weights dt |xi_dot|; tracers: acc = 0.0, weights |xi_dot|.
+template <class X>
+__device__ __forceinline__ double penalty_row(const double * ops, int L, int k, double acc, X x, double w_lo, double w_hi) {
+	if (k < L - 1) {
+		double b = 0.0;
+		b += op_coef(ops, L, TMX_OP_PENALTY_LEFT, k, 0) * x(0);
+		b += op_coef(ops, L, TMX_OP_PENALTY_LEFT, k, 1) * x(1);
+		acc += b * w_hi;
+	}
+	if (k > 0) {
+		double b = 0.0;
+		b += op_coef(ops, L, TMX_OP_PENALTY_RIGHT, k, -1) * x(-1);
+		b += op_coef(ops, L, TMX_OP_PENALTY_RIGHT, k, 0) * x(0);
+		acc += b * w_lo;
+	}
+	return acc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// UpdateColumnTracers (VerticalDynamicsFEM.cpp:3943-4233): the right-hand side of a tracer's column update, stated once for every
+// kernel of tmx_k_vertical.hip that evaluates it -- whichever way it spreads the work and wherever it keeps the operands.
+// Tracer flux through interface m (:4092-4140): J_e x (tracer density on the interface) x xi_dot, none through the boundaries; with
+// uniform diffusion (ud) minus K_s x (rho on the interface) x d/dxi of the mixing ratio's deviation from the reference column's.
+// qn(off), mixr(off): tracer density and that deviation on level m + off.
+template <class Q, class M>
+__device__ __forceinline__ double tracer_edge_flux(const double * ops, int L, int m, double je, double xd, bool ud, double ks, double re, Q qn, M mixr) {
+	const double qe = edge_sum(ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, qn);
+	double mf = (m == 0 || m == L) ? 0.0 : je * qe * xd;
+	if (ud && m > 0 && m < L) mf -= ks * re * edge_sum(ops, L, TMX_OP_DIFF_NODE_TO_REDGE, m, mixr);
+	return mf;
+}
+// Row k: the divergence of the fluxes through the interfaces k and k + 1 over J_n, minus the upwind penalty `aux` (penalty_row from 0.0)
+__device__ __forceinline__ double tracer_rhs_row(const double * ops, int L, int k, double mf_lo, double mf_hi, double jn, double aux) {
+	double dmf = 0.0;
+	dmf += op_coef(ops, L, TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf_lo;
+	dmf += op_coef(ops, L, TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf_hi;
+	double F = dmf / jn;
+	F -= aux;
+	return F;
+}
+// Row k for a thread that forms both of its fluxes itself: xdf(m) = xi_dot the flux is taken with, xdp(m) = xi_dot of the initial
+// column (the penalty's weight), re(m) = rho on interface m (read under ud only); here qn(l), mixr(l) take the level itself
+template <class Q, class M, class XF, class XP, class R>
+__device__ __forceinline__ double tracer_rhs_level(const double * ops, int L, int k, double je, double jn, bool ud, double ks, Q qn, M mixr, XF xdf, XP xdp, R re) {
+	double mf[2];
+#pragma unroll
+	for (int mo = 0; mo <= 1; mo++) {
+		const int m = k + mo;
+		mf[mo] = tracer_edge_flux(ops, L, m, je, xdf(m), ud, ks, ud ? re(m) : 0.0, [&](int off) { return qn(m + off); }, [&](int off) { return mixr(m + off); });
+	}
+	const double aux = penalty_row(ops, L, k, 0.0, [&](int d) { return qn(k + d); }, fabs(xdp(k)), fabs(xdp(k + 1)));
+	return tracer_rhs_row(ops, L, k, mf[0], mf[1], jn, aux);
+}
+// The fully explicit mode's "solve": the matrix is the diagonal 1/dt, dgbtrs leaves b_j / (1/dt) and skips a zero b_j
+__device__ __forceinline__ double tracer_explicit_solve(double F, double idt) {
+	if (F != 0.0) F /= idt;
+	return F;
+}
+
 // ---------------------------------------------------------------------------------------------
 // V explicit (implicit mode): xi_dot on interfaces and first-order upwind penalty on U,V
 // (src/atm/VerticalDynamicsFEM.cpp:816-828, 984-1023; LinearColumnOperatorFEM.cpp:1863-1888).
@@ -320,15 +400,8 @@ __device__ __forceinline__ double xidot_edge(const KParams & p, const double * _
 	const size_t NS = (size_t)p.NS;
 	if (kk <= 0 || kk >= L) return 0.0;
 	// U,V on interfaces = InterpolateNodeToREdge of the node values (H prologue, :817-831)
-	double ue = 0.0, ve = 0.0;
-#pragma unroll
-	for (int off = -2; off <= 1; off++) {
-		const int l = kk + off;
-		if (l < 0 || l >= L) continue;
-		const double c = OPC(TMX_OP_INTERP_NODE_TO_REDGE, kk, off);
-		ue += c * xin[TMX_SLAB_U(L, l) * NS + col];
-		ve += c * xin[TMX_SLAB_V(L, l) * NS + col];
-	}
+	const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, kk, [&](int off) { return xin[TMX_SLAB_U(L, kk + off) * NS + col]; });
+	const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, kk, [&](int off) { return xin[TMX_SLAB_V(L, kk + off) * NS + col]; });
 	const double we = xin[TMX_SLAB_W(L, kk) * NS + col];
 	double e0, e1, e2;
 	metric_edge(p, met_col(p, col), kk, col, e0, e1, e2);
@@ -354,21 +427,8 @@ __device__ __forceinline__ void v_explicit_point(const KParams & p, const double
 #pragma unroll
 	for (int v = 0; v < 2; v++) {
 		const int sb = v * L;
-		const double x0 = xin[(size_t)(sb + k) * NS + col];
-		const double xm = xin[(size_t)(sb + km) * NS + col], xp = xin[(size_t)(sb + kp) * NS + col];
-		double out = up0[v];
-		if (k < L - 1) {
-			double b = 0.0;
-			b += OPC(TMX_OP_PENALTY_LEFT, k, 0) * x0;
-			b += OPC(TMX_OP_PENALTY_LEFT, k, 1) * xp;
-			out += b * w_hi;
-		}
-		if (k > 0) {
-			double b = 0.0;
-			b += OPC(TMX_OP_PENALTY_RIGHT, k, -1) * xm;
-			b += OPC(TMX_OP_PENALTY_RIGHT, k, 0) * x0;
-			out += b * w_lo;
-		}
+		const double x3[3] = { xin[(size_t)(sb + km) * NS + col], xin[(size_t)(sb + k) * NS + col], xin[(size_t)(sb + kp) * NS + col] };
+		double out = penalty_row(p.ops, L, k, up0[v], [&](int d) { return x3[d + 1]; }, w_lo, w_hi);
 		if (UDV) {
 			double dd = 0.0, ddr = 0.0;
 #pragma unroll
@@ -384,6 +444,33 @@ __device__ __forceinline__ void v_explicit_point(const KParams & p, const double
 		xup[(size_t)(sb + k) * NS + col] = out;
 	}
 }
+
+// ---------------------------------------------------------------------------------------------
+// Frame of the kernels in which a thread walks a column, or one of `nseg` segments of it, row by row (k_v_explicit_slide,
+// k_v_tracers_explicit_slide, k_vi_terms_explicit_slide): workgroups of 64 columns x 2 segments, operator tables in LDS.
+// The operator tables and, CLOSED, the 1 - eta table go to LDS (`opsl`: [TMX_OP_COUNT][L + 1][TMX_OPW], `etal`: [2 L + 1]); the
+// caller's barrier follows.  The walks store to the update instance inside their loop, after which the compiler may not read the
+// tables through the scalar cache any more (the stores might alias them) -- and as vector loads each one waits for every load in
+// flight (s_waitcnt vmcnt(0)), the prefetched level included.
+template <bool CLOSED>
+__device__ __forceinline__ void walk_tables_to_lds(const KParams & p, double * opsl, double * etal) {
+	const int tid = threadIdx.y * 64 + threadIdx.x;
+	for (int t = tid; t < TMX_OP_COUNT * (p.L + 1) * TMX_OPW; t += 128) opsl[t] = p.ops[t];
+	if (CLOSED) for (int t = tid; t < 2 * p.L + 1; t += 128) etal[t] = p.eta[t];
+}
+// The thread's column and its rows k0 .. k1 - 1 of 0 .. rows - 1 (the two wavefronts of a workgroup: two segments of the same
+// columns); false: nothing to do
+__device__ __forceinline__ bool walk_segment(const KParams & p, int xmode, int ntile, int nseg, int rows, int & col, int & k0, int & k1) {
+	int bx, by;
+	if (!xcd_column_tile(xmode, ntile, (nseg + 1) / 2, bx, by)) return false;
+	col = (p.quads ? p.quads[bx] : bx) * 64 + threadIdx.x;
+	if (col >= p.ncol) return false;
+	const int sg = WAVE_UNIFORM(by * 2 + (int)threadIdx.y);
+	const int seg = (rows + nseg - 1) / nseg;
+	k0 = sg * seg; k1 = min(rows, k0 + seg);
+	return sg < nseg && k0 < k1;
+}
+
 
 
 // Ordering point for LDS rows that only ONE wavefront touches (the contraction rows s[ty][..] of the horizontal kernels, each

@@ -1013,6 +1013,11 @@ extern "C" int tmx_debug_h_walk_timing(tmx_engine * e, unsigned long long * out)
 	return TMX_OK;
 }
 
+// Host logic of the column walks, no device: the number of segments their launchers choose (walk_segments, tmx_internal.h)
+extern "C" int tmx_debug_walk_segments(int option, int ntiles, int rows, int target_wavefronts) {
+	return walk_segments(option, ntiles, rows, target_wavefronts);
+}
+
 // Statistics of the two-wavefront column kernel: how many pivot steps found the same pivot row in all 64 columns of a
 // wavefront (the renaming path) out of all pivot steps.  enable = 1 starts counting (zeroed), 0 stops; out (may be NULL)
 // receives {uniform, total} accumulated so far.

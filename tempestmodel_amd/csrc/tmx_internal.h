@@ -435,6 +435,15 @@ void tmxk_vi_assemble(tmx_engine * e, const KParams & p, const double * xin, dou
 void tmxk_vi_solve(tmx_engine * e, const KParams & p, const double * xin, double * xup);
 void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt);
 void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv = false);
+// The column walks (k_v_explicit_slide, k_v_tracers_explicit_slide, k_vi_terms_explicit_slide; frame: tmx_device.h): their LDS bytes (operator
+// tables, 1 - eta, the kernel's own tables) and the number of segments a column is walked in -- option -n = n segments, -1000 = in pairs
+// (the two wavefronts of a workgroup) until the grid has `target_wavefronts` of them, at least five rows each; 1 .. rows
+static inline size_t walk_lds_bytes(int L, int extra_doubles = 0) { return ((size_t)TMX_OP_COUNT * (L + 1) * TMX_OPW + 2 * L + 1 + extra_doubles) * sizeof(double); }
+static inline int walk_segments(int option, int ntiles, int rows, int target_wavefronts) {
+	int nseg = -option;
+	if (option == -1000) for (nseg = 2; ntiles * nseg < target_wavefronts && rows / (nseg + 2) >= 5; nseg += 2) { }
+	return nseg < 1 ? 1 : (nseg > rows ? rows : nseg);
+}
 void tmxk_dss(tmx_engine * e, const KParams & p, double * x, int g0, int g1);
 void tmxk_hypervis(tmx_engine * e, const KParams & p, const double * xsrc, const double * xbase, double * xout,
 	double dt, double nu_s, double nu_d, double nu_v, int scale_locally, bool pull_dss = false);

@@ -429,7 +429,6 @@ struct BlkCarry {
 
 // block row k from node levels A = k-1, B = k, C = k+1 and interfaces a = k-1, b = k, c = k+1
 // column-operator coefficients from the LDS copy (ds_read: no vector-memory round trip, no vmcnt wait behind the U-row stores)
-#define OPCL(op, k, off) opsl[(((op) * (p.L + 1)) + (k)) * TMX_OPW + ((off) + 2)]
 // UD: the uniform-diffusion terms of BuildF (VerticalDynamicsFEM.cpp:2593-2635), udP = K_s / ztop^2 * second derivative
 // of (rho*theta - reference) on level k, udW = K_v / ztop^2 * the same for W on interface k, subtracted where the
 // reference subtracts them (before the upwinding terms); only the fully explicit mode evaluates them.
@@ -626,7 +625,6 @@ __device__ __forceinline__ void compute_block(const KParams & p, const double * 
 #undef CBSTAMP
 }
 
-#undef OPCL
 
 // one elimination step on the register window (dgbtf2 + forward substitution of dgbtrs), then slide.
 // U rows go to the HBM scratch for the back substitution.  Entries 4..8 of a row are fill-in that exists only
@@ -1924,7 +1922,6 @@ __global__ __launch_bounds__(64 * KT_VC) void k_vi_terms_explicit(KParams p, con
 // value that has just left it, the three in it, the one about to enter) and keep sliding windows of the reference's.  A segment that
 // does not start at the bottom evaluates the block row below it first, only to fill the carry.  Same statements on the same
 // operands as k_vi_terms_explicit: bit-identical (tested).
-#define OPCL(op, k, off) opsl[(((op) * (p.L + 1)) + (k)) * TMX_OPW + ((off) + 2)]
 template <bool UD, bool CLOSED>
 __global__ __launch_bounds__(128) void k_vi_terms_explicit_slide(KParams p, const double * __restrict__ xin,
 	double * __restrict__ xup, double dt, const double * __restrict__ xref, double cs, double cw, int ntile, int xmode, int nseg)
@@ -1937,21 +1934,12 @@ __global__ __launch_bounds__(128) void k_vi_terms_explicit_slide(KParams p, cons
 	// the exp / log tables of the Exner function in LDS too: read from global memory each lookup is a vector-memory load behind an
 	// s_waitcnt vmcnt(0), i.e. two waits per block row for every level prefetch in flight (the column solve's assembly: the same)
 	double * rmtab = etal + 2 * L + 1;
-	{
-		const int tid = threadIdx.y * 64 + threadIdx.x;
-		for (int t = tid; t < TMX_OP_COUNT * (L + 1) * TMX_OPW; t += 128) opsl[t] = p.ops[t];
-		if (CLOSED) for (int t = tid; t < 2 * L + 1; t += 128) etal[t] = p.eta[t];
-		tmx_rm_tables_to_lds(rmtab, tid, 128);
-		__syncthreads();
-	}
+	walk_tables_to_lds<CLOSED>(p, opsl, etal);
+	tmx_rm_tables_to_lds(rmtab, threadIdx.y * 64 + threadIdx.x, 128);
+	__syncthreads();
 	const size_t NS = (size_t)p.NS;
-	int bx, by;
-	if (!xcd_column_tile(xmode, ntile, (nseg + 1) / 2, bx, by)) return;
-	const int col = (p.quads ? p.quads[bx] : bx) * 64 + threadIdx.x;
-	if (col >= p.ncol) return;
-	const int sg = WAVE_UNIFORM(by * 2 + (int)threadIdx.y);
-	const int seg = (L + 1 + nseg - 1) / nseg, k0 = sg * seg, k1 = min(L + 1, k0 + seg);      // block rows k0 .. k1 - 1 of 0 .. L
-	if (sg >= nseg || k0 >= k1) return;
+	int col, k0, k1;      // block rows k0 .. k1 - 1 of 0 .. L
+	if (!walk_segment(p, xmode, ntile, nseg, L + 1, col, k0, k1)) return;
 	ColConst cc;
 	cc.c2a0 = p.g2d[G2_C2A0 * NS + col]; cc.c2a1 = p.g2d[G2_C2A1 * NS + col]; cc.c2b1 = p.g2d[G2_C2B1 * NS + col];
 	cc.jn = p.g2d[G2_JN * NS + col]; cc.je = p.g2d[G2_JE * NS + col]; cc.drx = p.g2d[G2_DRX * NS + col];
@@ -2068,15 +2056,12 @@ __global__ __launch_bounds__(128) void k_vi_terms_explicit_slide(KParams p, cons
 		}
 	}
 }
-#undef OPCL
 
 void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv) {
 	const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
-	const size_t lds_slide = ((size_t)TMX_OP_COUNT * (p.L + 1) * TMX_OPW + 2 * p.L + 1 + TMX_RMTAB_DOUBLES) * sizeof(double);
+	const size_t lds_slide = walk_lds_bytes(p.L, TMX_RMTAB_DOUBLES);
 	if (e->opt_vite_walk < 0 && !with_uv && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
-		int nseg = -e->opt_vite_walk;
-		if (e->opt_vite_walk == -1000) for (nseg = 2; nt_ * nseg < 2048 && (p.L + 1) / (nseg + 2) >= 5; nseg += 2) { }
-		nseg = std::max(1, std::min(nseg, p.L + 1));
+		const int nseg = walk_segments(e->opt_vite_walk, nt_, p.L + 1, 2048);
 		dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
 		const bool ud = e->udiff && e->fully_explicit;
 		const double z2 = e->cfg.ztop * e->cfg.ztop;

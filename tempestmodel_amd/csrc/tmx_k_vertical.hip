@@ -39,8 +39,7 @@ __global__ __launch_bounds__(64 * KT_VE) void k_v_explicit(KParams p, const doub
 // The same update by a thread that walks a column (or one of `nseg` segments of it) level by level: U, V of the levels k - 2 .. k + 2
 // (and, UDV, the reference's) in a sliding register window, xi_dot of every interface evaluated once (the level-parallel form evaluates
 // it for the level below and again for the level above), the entering level loaded an iteration ahead, operator coefficients and
-// the 1 - eta table in LDS (see k_v_tracers_explicit_slide).  Same statements on the same operands as v_explicit_point: bit-identical (tested).
-#define OPCL(op, k, off) opsl[(((op) * (L + 1)) + (k)) * TMX_OPW + ((off) + 2)]
+// the 1 - eta table in LDS (walk_tables_to_lds).  The interface sums and the penalty row are v_explicit_point's (edge_sum, penalty_row: tmx_device.h).
 template <bool UDV, bool CLOSED>
 __global__ __launch_bounds__(128) void k_v_explicit_slide(KParams p, const double * __restrict__ xin, double * __restrict__ xup, double dt,
 	const double * __restrict__ xref, double cf, int ntile, int xmode, int nseg)
@@ -49,20 +48,11 @@ __global__ __launch_bounds__(128) void k_v_explicit_slide(KParams p, const doubl
 	const int L = p.L;
 	const size_t NS = (size_t)p.NS;
 	double * etal = opsl + TMX_OP_COUNT * (L + 1) * TMX_OPW;
-	{
-		const int tid = threadIdx.y * 64 + threadIdx.x;
-		for (int t = tid; t < TMX_OP_COUNT * (L + 1) * TMX_OPW; t += 128) opsl[t] = p.ops[t];
-		if (CLOSED) for (int t = tid; t < 2 * L + 1; t += 128) etal[t] = p.eta[t];
-		__syncthreads();
-	}
+	walk_tables_to_lds<CLOSED>(p, opsl, etal);
+	__syncthreads();
 	constexpr int MM = CLOSED ? 1 : 2;
-	int bx, by;
-	if (!xcd_column_tile(xmode, ntile, (nseg + 1) / 2, bx, by)) return;
-	const int col = (p.quads ? p.quads[bx] : bx) * 64 + threadIdx.x;
-	if (col >= p.ncol) return;
-	const int sg = WAVE_UNIFORM(by * 2 + (int)threadIdx.y);
-	const int seg = (L + nseg - 1) / nseg, k0 = sg * seg, k1 = min(L, k0 + seg);
-	if (sg >= nseg || k0 >= k1) return;
+	int col, k0, k1;
+	if (!walk_segment(p, xmode, ntile, nseg, L, col, k0, k1)) return;
 	const MetCol mc = met_col(p, col);
 	auto in = [&](int l) { return l >= 0 && l < L; };
 	// window: levels k - 2 .. k + 2, at the (virtual) level k = k0 - 1 the walk starts from
@@ -91,15 +81,8 @@ __global__ __launch_bounds__(128) void k_v_explicit_slide(KParams p, const doubl
 		// xi_dot on interface m (xidot_edge): window entries 1 .. 4 are the levels m - 2 .. m + 1
 		double xd_hi = 0.0;
 		if (m >= 1 && m <= L - 1) {
-			double ue = 0.0, ve = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				const double c = OPCL(TMX_OP_INTERP_NODE_TO_REDGE, m, off);
-				ue += c * uw[off + 3];
-				ve += c * vw[off + 3];
-			}
+			const double ue = edge_sum(opsl, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return uw[off + 3]; });
+			const double ve = edge_sum(opsl, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return vw[off + 3]; });
 			double e0, e1, e2;
 			metric_edge<MM>(p, mc, m, col, e0, e1, e2, etal);
 			xd_hi = e0 * ue + e1 * ve + e2 * wm;
@@ -110,20 +93,7 @@ __global__ __launch_bounds__(128) void k_v_explicit_slide(KParams p, const doubl
 #pragma unroll
 			for (int v = 0; v < 2; v++) {
 				const double * x = v ? vw : uw, * xr = v ? vr : ur;
-				const double x0 = x[2], xm = x[1], xp = x[3];
-				double out = v ? upV : upU;
-				if (k < L - 1) {
-					double b = 0.0;
-					b += OPCL(TMX_OP_PENALTY_LEFT, k, 0) * x0;
-					b += OPCL(TMX_OP_PENALTY_LEFT, k, 1) * xp;
-					out += b * w_hi;
-				}
-				if (k > 0) {
-					double b = 0.0;
-					b += OPCL(TMX_OP_PENALTY_RIGHT, k, -1) * xm;
-					b += OPCL(TMX_OP_PENALTY_RIGHT, k, 0) * x0;
-					out += b * w_lo;
-				}
+				double out = penalty_row(opsl, L, k, v ? upV : upU, [&](int d) { return x[d + 2]; }, w_lo, w_hi);
 				if (UDV) {
 					double dd = 0.0, ddr = 0.0;
 #pragma unroll
@@ -149,17 +119,14 @@ __global__ __launch_bounds__(128) void k_v_explicit_slide(KParams p, const doubl
 		if (k >= k0) { xup[(size_t)k * NS + col] = res[0]; xup[(size_t)(L + k) * NS + col] = res[1]; }
 	}
 }
-#undef OPCL
 
 void tmxk_v_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_udiff_uv) {
 	const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
-	const size_t lds_slide = ((size_t)TMX_OP_COUNT * (p.L + 1) * TMX_OPW + 2 * p.L + 1) * sizeof(double);
+	const size_t lds_slide = walk_lds_bytes(p.L);
 	if (e->opt_vx_walk < 0 && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
-		int nseg = -e->opt_vx_walk;
 		// (a light kernel, four resident wavefronts per SIMD: ne30 L40 on one GPU 1 / 2 / 4 segments 3.84 / 3.76 / 3.75 ms per step of BASELINE config 4's
 		// shape, the level-parallel kernel 3.98)
-		if (e->opt_vx_walk == -1000) for (nseg = 2; nt_ * nseg < 4096 && p.L / (nseg + 2) >= 5; nseg += 2) { }
-		nseg = std::max(1, std::min(nseg, p.L));
+		const int nseg = walk_segments(e->opt_vx_walk, nt_, p.L, 4096);
 		dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
 		const double cf = with_udiff_uv ? e->cfg.uniform_diffusion_vector / (e->cfg.ztop * e->cfg.ztop) : 0.0;
 #define LAUNCH_VXS(UD_, CL_) hipLaunchKernelGGL((k_v_explicit_slide<UD_, CL_>), grd, blk, lds_slide, e->stream, p, xin, xup, dt, (const double *)(with_udiff_uv ? e->d_ref : nullptr), cf, nt_, xm, nseg)
@@ -201,15 +168,8 @@ __global__ __launch_bounds__(64) void k_vi_tracers(KParams p, int nt, const doub
 	for (int k = 0; k <= L; k++) {
 		double x0v = 0.0, x1v = 0.0;
 		if (k >= 1 && k <= L - 1) {
-			double ue = 0.0, ve = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = k + off;
-				if (l < 0 || l >= L) continue;
-				const double cc = OPC(TMX_OP_INTERP_NODE_TO_REDGE, k, off);
-				ue += cc * xin[(size_t)TMX_SLAB_U(L, l) * NS + col];
-				ve += cc * xin[(size_t)TMX_SLAB_V(L, l) * NS + col];
-			}
+			const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_U(L, k + off) * NS + col]; });
+			const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_V(L, k + off) * NS + col]; });
 			double e0, e1, e2;
 			metric_edge(p, mc, k, col, e0, e1, e2);
 			x0v = e0 * ue + e1 * ve + e2 * w0[(size_t)k * NS + col];
@@ -251,16 +211,8 @@ __global__ __launch_bounds__(64) void k_vi_tracers(KParams p, int nt, const doub
 	unsigned long long jpmask = 0, jpmask_hi = 0, zeromask = 0, zeromask_hi = 0;      // interchanges / zero pivots of the factorisation, by column
 	if (expl && ks != 0.0) {
 		// rho on interfaces: InterpolateNodeToREdge of the initial column (PrepareColumn :1905-1916)
-		for (int m = 0; m <= L; m++) {
-			double re = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				re += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * xin[(size_t)TMX_SLAB_R(L, l) * NS + col];
-			}
-			rhoe[(size_t)m * LW + lane] = re;
-		}
+		for (int m = 0; m <= L; m++)
+			rhoe[(size_t)m * LW + lane] = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_R(L, m + off) * NS + col]; });
 	}
 	for (int c = 0; c < nt; c++) {
 		for (int k = 0; k < L; k++) qn[(size_t)k * LW + lane] = xin[(size_t)TMX_SLAB_Q(L, c, k) * NS + col];
@@ -270,60 +222,17 @@ __global__ __launch_bounds__(64) void k_vi_tracers(KParams p, int nt, const doub
 				a -= xref[(size_t)TMX_SLAB_Q(L, c, k) * NS + col] / xref[(size_t)TMX_SLAB_R(L, k) * NS + col];
 				mixr[(size_t)k * LW + lane] = a;
 			}
-		// mass flux with the updated xi_dot, its divergence (:4092-4140)
-		for (int k = 0; k < L; k++) {
-			double mf[2];
-			for (int mo = 0; mo <= 1; mo++) {
-				const int m = k + mo;
-				double qe = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					qe += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * qn[(size_t)l * LW + lane];
-				}
-				mf[mo] = (m == 0 || m == L) ? 0.0 : je * qe * xd1[(size_t)m * LW + lane];
-				if (expl && ks != 0.0 && m > 0 && m < L) {
-					double dq = 0.0;       // DifferentiateNodeToREdge of the mixing-ratio difference
-#pragma unroll
-					for (int off = -2; off <= 1; off++) {
-						const int l = m + off;
-						if (l < 0 || l >= L) continue;
-						dq += OPC(TMX_OP_DIFF_NODE_TO_REDGE, m, off) * mixr[(size_t)l * LW + lane];
-					}
-					mf[mo] -= ks * rhoe[(size_t)m * LW + lane] * dq;
-				}
-			}
-			double dmf = 0.0;
-			dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf[0];
-			dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf[1];
-			F[(size_t)k * LW + lane] = dmf / jn;
-		}
-		// upwinding with the initial xi_dot (LinearColumnDiscPenaltyFEM::Apply; :4153-4181)
-		for (int k = 0; k < L; k++) {
-			double aux = 0.0;
-			if (k < L - 1) {
-				double b = 0.0;
-				b += OPC(TMX_OP_PENALTY_LEFT, k, 0) * qn[(size_t)k * LW + lane];
-				b += OPC(TMX_OP_PENALTY_LEFT, k, 1) * qn[(size_t)(k + 1) * LW + lane];
-				aux += b * fabs(xd0[(size_t)(k + 1) * LW + lane]);
-			}
-			if (k > 0) {
-				double b = 0.0;
-				b += OPC(TMX_OP_PENALTY_RIGHT, k, -1) * qn[(size_t)(k - 1) * LW + lane];
-				b += OPC(TMX_OP_PENALTY_RIGHT, k, 0) * qn[(size_t)k * LW + lane];
-				aux += b * fabs(xd0[(size_t)k * LW + lane]);
-			}
-			F[(size_t)k * LW + lane] -= aux;
-		}
+		// mass flux with the updated xi_dot, its divergence (:4092-4140), upwinding with the initial xi_dot (:4153-4181): tracer_rhs_level
+		for (int k = 0; k < L; k++)
+			F[(size_t)k * LW + lane] = tracer_rhs_level(p.ops, L, k, je, jn, expl && ks != 0.0, ks,
+				[&](int l) { return qn[(size_t)l * LW + lane]; }, [&](int l) { return mixr[(size_t)l * LW + lane]; },
+				[&](int m) { return xd1[(size_t)m * LW + lane]; }, [&](int m) { return xd0[(size_t)m * LW + lane]; }, [&](int m) { return rhoe[(size_t)m * LW + lane]; });
 		if (expl) {
 			// diagonal matrix 1/dt: dgbtrs leaves b_j / (1/dt)
 			const double idt = 1.0 / dt;
 			for (int k = 0; k < L; k++) {
 				const size_t so = (size_t)TMX_SLAB_Q(L, c, k) * NS;
-				double bj = F[(size_t)k * LW + lane];
-				if (bj != 0.0) bj /= idt;
-				xup[so + col] = xbase[so + col] - bj;
+				xup[so + col] = xbase[so + col] - tracer_explicit_solve(F[(size_t)k * LW + lane], idt);
 			}
 			continue;
 		}
@@ -436,15 +345,8 @@ template <int NR, int LWB> __global__ __launch_bounds__(NR << LWB) void k_vi_tra
 	for (int k = t; k <= L; k += NR) {
 		double x0v = 0.0, x1v = 0.0, jv = 0.0;
 		if (k >= 1 && k <= L - 1) {
-			double ue = 0.0, ve = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = k + off;
-				if (l < 0 || l >= L) continue;
-				const double cc = OPC(TMX_OP_INTERP_NODE_TO_REDGE, k, off);
-				ue += cc * xin[(size_t)TMX_SLAB_U(L, l) * NS + col];
-				ve += cc * xin[(size_t)TMX_SLAB_V(L, l) * NS + col];
-			}
+			const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_U(L, k + off) * NS + col]; });
+			const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_V(L, k + off) * NS + col]; });
 			double e0, e1, e2;
 			metric_edge(p, mc, k, col, e0, e1, e2);
 			const double wi = w0[(size_t)k * NS + col], wu = xup[(size_t)TMX_SLAB_W(L, k) * NS + col];
@@ -526,39 +428,10 @@ template <int NR, int LWB> __global__ __launch_bounds__(NR << LWB) void k_vi_tra
 		for (int k = t; k < L; k += NR) qn[(size_t)k * LW + lane] = xin[(size_t)TMX_SLAB_Q(L, c, k) * NS + col];
 		__syncthreads();
 		for (int k = t; k < L; k += NR) {
-			// mass flux with the updated xi_dot, its divergence (:4092-4140)
-			double mf[2];
-#pragma unroll
-			for (int mo = 0; mo <= 1; mo++) {
-				const int m = k + mo;
-				double qe = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					qe += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * qn[(size_t)l * LW + lane];
-				}
-				mf[mo] = (m == 0 || m == L) ? 0.0 : je * qe * xd1[(size_t)m * LW + lane];
-			}
-			double dmf = 0.0;
-			dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf[0];
-			dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf[1];
-			double f = dmf / jn;
-			// upwinding with the initial xi_dot (:4153-4181)
-			double aux = 0.0;
-			if (k < L - 1) {
-				double b = 0.0;
-				b += OPC(TMX_OP_PENALTY_LEFT, k, 0) * qn[(size_t)k * LW + lane];
-				b += OPC(TMX_OP_PENALTY_LEFT, k, 1) * qn[(size_t)(k + 1) * LW + lane];
-				aux += b * fabs(xd0[(size_t)(k + 1) * LW + lane]);
-			}
-			if (k > 0) {
-				double b = 0.0;
-				b += OPC(TMX_OP_PENALTY_RIGHT, k, -1) * qn[(size_t)(k - 1) * LW + lane];
-				b += OPC(TMX_OP_PENALTY_RIGHT, k, 0) * qn[(size_t)k * LW + lane];
-				aux += b * fabs(xd0[(size_t)k * LW + lane]);
-			}
-			f -= aux;
+			// mass flux with the updated xi_dot, its divergence (:4092-4140), upwinding with the initial xi_dot (:4153-4181): tracer_rhs_level
+			auto qcol = [&](int l) { return qn[(size_t)l * LW + lane]; };
+			double f = tracer_rhs_level(p.ops, L, k, je, jn, false, 0.0, qcol, qcol,
+				[&](int m) { return xd1[(size_t)m * LW + lane]; }, [&](int m) { return xd0[(size_t)m * LW + lane]; }, [](int) { return 0.0; });
 			// implicit velocity correction (:4183-4233): interface a = k (this row as "a"), then a = k + 1 (as "a - 1")
 #pragma unroll
 			for (int s_ = 0; s_ <= 1; s_++) {
@@ -619,63 +492,62 @@ template <int NR, int LWB> __global__ __launch_bounds__(NR << LWB) void k_vi_tra
 #undef AR
 }
 
-static size_t vt_rows_lds(int L, int lw = 16) { return ((size_t)L * 4 + (size_t)L * 2 + (size_t)(L + 1) * 3) * lw * sizeof(double); }
+// LDS working set of the column kernels per workgroup of lw columns: band matrix [L][4], right-hand side and tracer column [L] each,
+// nedge arrays on the interfaces [L + 1] (xi_dot initial / updated: (8L + 2) x lw doubles; k_vi_tracers_rows: the velocity jump too, (9L + 3) x lw)
+static size_t vt_lds(int L, int lw, int nedge) { return ((size_t)L * 4 + (size_t)L * 2 + (size_t)(L + 1) * nedge) * lw * sizeof(double); }
+
+// The columns a launch updates: all of them (ucol == nullptr), or the unique ones with up to three dependents each that receive a copy
+struct ColumnSet { int ncols; const int * ucol, * udep; };
+
 // row lanes per column of k_vi_tracers_rows: 16 (four wavefronts per 16 columns) up to 48 levels, 32 above; TMX_VT_NR = 4 | 8 | 16 | 32;
 // 8 columns per workgroup up to 48 levels (half the LDS per workgroup, twice the workgroups per CU), 16 above; TMX_VT_LW8 = 0 | 1
-static void launch_vt_rows(tmx_engine * e, const KParams & p, int ncols, const double * xin, const double * w0, const double * xbase, double * xup,
-	double dt, const int * ucol, const int * udep, size_t lds)
-{
+static void launch_vt_rows(tmx_engine * e, const KParams & p, const ColumnSet & cs, const double * xin, const double * w0, const double * xbase, double * xup, double dt) {
 	const int nr_env = e->opt_vt_nr, lw8_env = e->opt_vt_lw8;      // options "vt_row_lanes", "vt_lw8"
 	const bool lw8 = lw8_env >= 0 ? lw8_env == 1 : p.L <= 48;    // ne30, 2 tracers: L30 1.308 (8 columns) / 1.358 (16) ms per step, L60 3.35 / 3.21
 	const int nr = nr_env ? nr_env : (p.L > 48 ? 32 : 16);       // measured at ne30: L30 1.36 (16) / 1.49 (32) ms, L60 3.50 (16) / 3.25 (32) ms per step
 #define LAUNCH_VTR(NR_, LWB_) do { \
-		const size_t lds_ = vt_rows_lds(p.L, 1 << LWB_); \
-		hipFuncSetAttribute((const void *)k_vi_tracers_rows<NR_, LWB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-		hipLaunchKernelGGL((k_vi_tracers_rows<NR_, LWB_>), dim3((ncols + (1 << LWB_) - 1) >> LWB_), dim3(NR_ << LWB_), lds_, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \
-			ncols, ucol, udep, e->d_flag); } while (0)
+		const size_t lds_ = vt_lds(p.L, 1 << LWB_, 3); \
+		(void)hipFuncSetAttribute((const void *)k_vi_tracers_rows<NR_, LWB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
+		hipLaunchKernelGGL((k_vi_tracers_rows<NR_, LWB_>), dim3((cs.ncols + (1 << LWB_) - 1) >> LWB_), dim3(NR_ << LWB_), lds_, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \
+			cs.ncols, cs.ucol, cs.udep, e->d_flag); } while (0)
 	if (lw8) { if (nr == 8) LAUNCH_VTR(8, 3); else if (nr == 32) LAUNCH_VTR(32, 3); else LAUNCH_VTR(16, 3); }
 	else if (nr == 4) LAUNCH_VTR(4, 4); else if (nr == 8) LAUNCH_VTR(8, 4); else if (nr == 32) LAUNCH_VTR(32, 4); else LAUNCH_VTR(16, 4);
 #undef LAUNCH_VTR
 }
 
-// lanes per workgroup such that the LDS working set (8L + 2) x LW x 8 bytes fits one CU
-static int vi_tracers_lanes(int L, size_t & lds) {
-	for (int lw = 64; lw >= 32; lw >>= 1) {
-		lds = ((size_t)L * 4 + (size_t)L * 2 + (size_t)(L + 1) * 2) * lw * sizeof(double);
-		if (lds <= 160 * 1024) return lw;
-	}
-	return 0;
-}
-
-int tmxk_vi_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * w0, const double * xbase, double * xup, double dt) {
-	if (e->nunique == 0 || e->nt == 0) return 0;
-	if (e->opt_vt_rows) {      // default: 16 columns x 4 row lanes per workgroup
-		const size_t l2 = vt_rows_lds(p.L);
-		if (l2 <= 160 * 1024) {
-			launch_vt_rows(e, p, e->nunique, xin, w0, xbase, xup, dt, (const int *)e->d_ucol, (const int *)e->d_udep, l2);
-			return 0;
-		}
-	}
-	size_t lds; int lw = vi_tracers_lanes(p.L, lds);
+// The column update of the tracers on a set of columns by the LDS kernels.  Implicit mode (expl = false): k_vi_tracers_rows (option
+// "vt_rows", the default, where its 16-column working set fits a CU), else k_vi_tracers; explicit mode (ks, xref: uniform diffusion):
+// k_vi_tracers.  k_vi_tracers takes the most lanes (64 or 32) whose working set fits one CU; `lanes` = 32 | 16 | 8 asks for fewer.
+// Fewer columns per workgroup = more workgroups per CU: the kernel lives in LDS (dependent read-modify-write chains of ~100 cycles
+// each) and one 64-column workgroup fills a CU's LDS, i.e. ONE wavefront per CU.  With 16 columns per workgroup five wavefronts
+// share a CU and hide each other's LDS latency.  Returns -1 where no shape fits.
+static int launch_vt_columns(tmx_engine * e, const KParams & p, const ColumnSet & cs, const double * xin, const double * w0, const double * xbase, double * xup,
+	double dt, bool expl, double ks, const double * xref, int lanes)
+{
+	if (!expl && e->opt_vt_rows && vt_lds(p.L, 16, 3) <= 160 * 1024) { launch_vt_rows(e, p, cs, xin, w0, xbase, xup, dt); return 0; }
+	int lw = 0;
+	for (int l = 64; l >= 32 && !lw; l >>= 1) if (vt_lds(p.L, l, 2) <= 160 * 1024) lw = l;
 	if (!lw) return -1;
-	// Fewer columns per workgroup = more workgroups per CU: the kernel lives in LDS (dependent read-modify-write chains of
-	// ~100 cycles each) and one 64-column workgroup fills a CU's LDS, i.e. ONE wavefront per CU.  With 16 columns per
-	// workgroup five wavefronts share a CU and hide each other's LDS latency (TMX_VT_LANES: 64, 32, 16, 8 for A/B).
-	int want = 16;
-	want = e->opt_vt_lanes;
-	if (want < lw && (want == 32 || want == 16 || want == 8)) { lw = want; lds = ((size_t)p.L * 4 + (size_t)p.L * 2 + (size_t)(p.L + 1) * 2) * lw * sizeof(double); }
-#define LAUNCH_VT(LW_) do { hipFuncSetAttribute((const void *)k_vi_tracers<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-	hipLaunchKernelGGL(k_vi_tracers<LW_>, dim3((e->nunique + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \
-		e->nunique, (const int *)e->d_ucol, (const int *)e->d_udep, e->d_flag, 0, 0.0, (const double *)nullptr); } while (0)
+	if (lanes < lw && (lanes == 32 || lanes == 16 || lanes == 8)) lw = lanes;
+	const size_t lds = vt_lds(p.L, lw, 2);
+#define LAUNCH_VT(LW_) do { (void)hipFuncSetAttribute((const void *)k_vi_tracers<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+	hipLaunchKernelGGL(k_vi_tracers<LW_>, dim3((cs.ncols + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \
+		cs.ncols, cs.ucol, cs.udep, e->d_flag, expl ? 1 : 0, ks, xref); } while (0)
 	if (lw == 64) LAUNCH_VT(64); else if (lw == 32) LAUNCH_VT(32); else if (lw == 16) LAUNCH_VT(16); else LAUNCH_VT(8);
 #undef LAUNCH_VT
 	return 0;
 }
 
+// UpdateColumnTracers behind the implicit column solve: the unique columns, their dependents written along (option "vt_lanes", default 16)
+int tmxk_vi_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * w0, const double * xbase, double * xup, double dt) {
+	if (e->nunique == 0 || e->nt == 0) return 0;
+	return launch_vt_columns(e, p, ColumnSet{ e->nunique, (const int *)e->d_ucol, (const int *)e->d_udep }, xin, w0, xbase, xup, dt, false, 0.0, nullptr, e->opt_vt_lanes);
+}
+
 #if TMX_EXP      // the form without LDS staging (option "vt_explicit_v1"), superseded by k_v_tracers_explicit_tile: experiments flavour only
 // UpdateColumnTracers in the fully explicit vertical mode, level-parallel.  There the matrix is the diagonal 1/dt, so the
 // update of (column, level, tracer) only needs the column within two levels: one thread per (column, level) evaluates
-// exactly the statements of k_vi_tracers' explicit branch (same operands, same order: bit-identical, tested) instead of one
+// the right-hand side of k_vi_tracers' explicit branch (tracer_rhs_level, tmx_device.h) instead of one
 // lane walking the whole column out of LDS -- that form took 3.4 ms per launch at ne30 L40 (32 columns per workgroup, 82 KB
 // of LDS each), 75 % of a supercell step.
 __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, const double * __restrict__ xin, double * xup, double dt,
@@ -696,15 +568,8 @@ __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, c
 		const int m = k + mo;
 		double x0v = 0.0;
 		if (m >= 1 && m <= L - 1) {
-			double ue = 0.0, ve = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				const double cc = OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off);
-				ue += cc * xin[(size_t)TMX_SLAB_U(L, l) * NS + col];
-				ve += cc * xin[(size_t)TMX_SLAB_V(L, l) * NS + col];
-			}
+			const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_U(L, m + off) * NS + col]; });
+			const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_V(L, m + off) * NS + col]; });
 			double e0, e1, e2;
 			metric_edge(p, mc, m, col, e0, e1, e2);
 			x0v = e0 * ue + e1 * ve + e2 * w0[(size_t)m * NS + col];
@@ -715,17 +580,7 @@ __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, c
 	double rhoe[2] = { 0.0, 0.0 };
 	if (ks != 0.0) {
 #pragma unroll
-		for (int mo = 0; mo <= 1; mo++) {
-			const int m = k + mo;
-			double re = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				re += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * xin[(size_t)TMX_SLAB_R(L, l) * NS + col];
-			}
-			rhoe[mo] = re;
-		}
+		for (int mo = 0; mo <= 1; mo++) rhoe[mo] = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k + mo, [&](int off) { return xin[(size_t)TMX_SLAB_R(L, k + mo + off) * NS + col]; });
 	}
 	// rho of the five levels k-2 .. k+2 the stencils reach (each value is loaded once and divided once per tracer)
 	double rh5[5] = { 1.0, 1.0, 1.0, 1.0, 1.0 }, rr5[5] = { 1.0, 1.0, 1.0, 1.0, 1.0 };
@@ -753,49 +608,8 @@ __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, c
 		}
 		auto qn = [&](int l) -> double { return q5[l - k + 2]; };          // l in [k-2, k+2], unrolled: a register
 		auto mixr = [&](int l) -> double { return mr5[l - k + 2]; };
-		double mf[2];
-#pragma unroll
-		for (int mo = 0; mo <= 1; mo++) {
-			const int m = k + mo;
-			double qe = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				qe += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * qn(l);
-			}
-			mf[mo] = (m == 0 || m == L) ? 0.0 : je * qe * xd[mo];
-			if (ks != 0.0 && m > 0 && m < L) {
-				double dq = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					dq += OPC(TMX_OP_DIFF_NODE_TO_REDGE, m, off) * mixr(l);
-				}
-				mf[mo] -= ks * rhoe[mo] * dq;
-			}
-		}
-		double dmf = 0.0;
-		dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf[0];
-		dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf[1];
-		double F = dmf / jn;
-		double aux = 0.0;
-		if (k < L - 1) {
-			double b = 0.0;
-			b += OPC(TMX_OP_PENALTY_LEFT, k, 0) * qn(k);
-			b += OPC(TMX_OP_PENALTY_LEFT, k, 1) * qn(k + 1);
-			aux += b * fabs(xd[1]);
-		}
-		if (k > 0) {
-			double b = 0.0;
-			b += OPC(TMX_OP_PENALTY_RIGHT, k, -1) * qn(k - 1);
-			b += OPC(TMX_OP_PENALTY_RIGHT, k, 0) * qn(k);
-			aux += b * fabs(xd[0]);
-		}
-		F -= aux;
-		const double idt = 1.0 / dt;
-		if (F != 0.0) F /= idt;
+		const double F = tracer_explicit_solve(tracer_rhs_level(p.ops, L, k, je, jn, ks != 0.0, ks, qn, mixr,
+			[&](int m) { return xd[m - k]; }, [&](int m) { return xd[m - k]; }, [&](int m) { return rhoe[m - k]; }), 1.0 / dt);
 		const size_t so = (size_t)TMX_SLAB_Q(L, c, k) * NS;
 		xup[so + col] = xup[so + col] - F;
 	}
@@ -805,7 +619,7 @@ __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, c
 // The same update (k_v_tracers_explicit, experiments flavour: one thread per (column, level) with every operand from memory) with the shared operands of a tile staged once in LDS: a workgroup = 64 columns x 8 levels; xi_dot (and, with
 // uniform diffusion, rho) on the tile's 9 interfaces, rho on its 12 levels and per tracer the 12 column values and mixing-ratio
 // deviations (two fp64 divisions each) are evaluated by one thread each instead of by every thread whose stencil reaches them
-// (5 x for the divisions: 372 -> 264 us per launch at ne30 L40 with three tracers).  Every value is produced by the same expression as above, so the results are bit-identical.
+// (5 x for the divisions: 372 -> 264 us per launch at ne30 L40 with three tracers).  The right-hand side itself is tracer_rhs_level (tmx_device.h), as in k_vi_tracers.
 __global__ __launch_bounds__(512) void k_v_tracers_explicit_tile(KParams p, int nt, const double * __restrict__ xin, double * xup, double dt,
 	double ks, const double * __restrict__ xref, int ntile, int xmode)
 {
@@ -842,27 +656,13 @@ __global__ __launch_bounds__(512) void k_v_tracers_explicit_tile(KParams p, int 
 			const int m = k0 + mi;
 			double x0v = 0.0, re = 0.0;
 			if (m >= 1 && m <= L - 1) {
-				double ue = 0.0, ve = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					const double cc = OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off);
-					ue += cc * xin[(size_t)TMX_SLAB_U(L, l) * NS + col];
-					ve += cc * xin[(size_t)TMX_SLAB_V(L, l) * NS + col];
-				}
+				const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_U(L, m + off) * NS + col]; });
+				const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_V(L, m + off) * NS + col]; });
 				double e0, e1, e2;
 				metric_edge(p, mc, m, col, e0, e1, e2);
 				x0v = e0 * ue + e1 * ve + e2 * w0[(size_t)m * NS + col];
 			}
-			if (ks != 0.0 && m <= L) {
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					re += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * xin[(size_t)TMX_SLAB_R(L, l) * NS + col];
-				}
-			}
+			if (ks != 0.0 && m <= L) re = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_R(L, m + off) * NS + col]; });
 			s_xd[mi][tx] = x0v; s_re[mi][tx] = re;
 		}
 		for (int li = y; li < NL; li += KT) {
@@ -895,49 +695,8 @@ __global__ __launch_bounds__(512) void k_v_tracers_explicit_tile(KParams p, int 
 		if (k >= L || col >= p.ncol) continue;
 		auto qn = [&](int l) -> double { return s_q[l - k0 + 2][tx]; };
 		auto mixr = [&](int l) -> double { return s_mr[l - k0 + 2][tx]; };
-		double mf[2];
-#pragma unroll
-		for (int mo = 0; mo <= 1; mo++) {
-			const int m = k + mo;
-			double qe = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				qe += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * qn(l);
-			}
-			mf[mo] = (m == 0 || m == L) ? 0.0 : je * qe * s_xd[y + mo][tx];
-			if (ks != 0.0 && m > 0 && m < L) {
-				double dq = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					dq += OPC(TMX_OP_DIFF_NODE_TO_REDGE, m, off) * mixr(l);
-				}
-				mf[mo] -= ks * s_re[y + mo][tx] * dq;
-			}
-		}
-		double dmf = 0.0;
-		dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf[0];
-		dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf[1];
-		double F = dmf / jn;
-		double aux = 0.0;
-		if (k < L - 1) {
-			double b = 0.0;
-			b += OPC(TMX_OP_PENALTY_LEFT, k, 0) * qn(k);
-			b += OPC(TMX_OP_PENALTY_LEFT, k, 1) * qn(k + 1);
-			aux += b * fabs(s_xd[y + 1][tx]);
-		}
-		if (k > 0) {
-			double b = 0.0;
-			b += OPC(TMX_OP_PENALTY_RIGHT, k, -1) * qn(k - 1);
-			b += OPC(TMX_OP_PENALTY_RIGHT, k, 0) * qn(k);
-			aux += b * fabs(s_xd[y][tx]);
-		}
-		F -= aux;
-		const double idt = 1.0 / dt;
-		if (F != 0.0) F /= idt;
+		const double F = tracer_explicit_solve(tracer_rhs_level(p.ops, L, k, je, jn, ks != 0.0, ks, qn, mixr,
+			[&](int m) { return s_xd[m - k0][tx]; }, [&](int m) { return s_xd[m - k0][tx]; }, [&](int m) { return s_re[m - k0][tx]; }), 1.0 / dt);
 		const size_t so = (size_t)TMX_SLAB_Q(L, c, k) * NS;
 		xup[so + col] = up0 - F;
 	}
@@ -947,8 +706,8 @@ __global__ __launch_bounds__(512) void k_v_tracers_explicit_tile(KParams p, int 
 // The same update by column segments: a thread = (column, KC consecutive levels), no LDS and no barrier.  The operands a segment's
 // stencils reach -- U, V, rho on KC + 3 / KC + 4 levels, per tracer the KC + 4 column values and mixing-ratio deviations -- are loaded
 // once into registers and every interface flux is formed once (the level-parallel forms evaluate the flux of interface k + 1 for level
-// k and again for level k + 1: the same expression on the same operands, so once is the same value).  Statement for statement the
-// arithmetic of k_v_tracers_explicit_tile: bit-identical (tested).
+// k and again for level k + 1: the same expression on the same operands, so once is the same value): tracer_edge_flux, then
+// penalty_row and tracer_rhs_row (tmx_device.h), the pieces of the level-parallel forms' tracer_rhs_level.
 template <int KC>
 __global__ __launch_bounds__(64) void k_v_tracers_explicit_walk(KParams p, int nt, const double * __restrict__ xin, double * xup, double dt,
 	double ks, const double * __restrict__ xref, int ntile, int xmode)
@@ -986,27 +745,13 @@ __global__ __launch_bounds__(64) void k_v_tracers_explicit_walk(KParams p, int n
 			const int m = k0 + mi;
 			double x0v = 0.0, r0 = 0.0;
 			if (mi <= nk && m >= 1 && m <= L - 1) {
-				double ue = 0.0, ve = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					const double cc = OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off);
-					ue += cc * uw[mi + off + 2];
-					ve += cc * vw[mi + off + 2];
-				}
+				const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return uw[mi + off + 2]; });
+				const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return vw[mi + off + 2]; });
 				double e0, e1, e2;
 				metric_edge(p, mc, m, col, e0, e1, e2);
 				x0v = e0 * ue + e1 * ve + e2 * w0[(size_t)m * NS + col];
 			}
-			if (ks != 0.0 && mi <= nk && m <= L) {
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					r0 += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * rh[mi + off + 2];
-				}
-			}
+			if (ks != 0.0 && mi <= nk && m <= L) r0 = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return rh[mi + off + 2]; });
 			xd[mi] = x0v; re[mi] = r0;
 		}
 	}
@@ -1033,51 +778,15 @@ __global__ __launch_bounds__(64) void k_v_tracers_explicit_walk(KParams p, int n
 		for (int mi = 0; mi < NI; mi++) {
 			const int m = k0 + mi;
 			double v = 0.0;
-			if (mi <= nk) {
-				double qe = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					qe += OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * q[mi + off + 2];
-				}
-				v = (m == 0 || m == L) ? 0.0 : je * qe * xd[mi];
-				if (ks != 0.0 && m > 0 && m < L) {
-					double dq = 0.0;
-#pragma unroll
-					for (int off = -2; off <= 1; off++) {
-						const int l = m + off;
-						if (l < 0 || l >= L) continue;
-						dq += OPC(TMX_OP_DIFF_NODE_TO_REDGE, m, off) * mr[mi + off + 2];
-					}
-					v -= ks * re[mi] * dq;
-				}
-			}
+			if (mi <= nk) v = tracer_edge_flux(p.ops, L, m, je, xd[mi], ks != 0.0, ks, re[mi], [&](int off) { return q[mi + off + 2]; }, [&](int off) { return mr[mi + off + 2]; });
 			mf[mi] = v;
 		}
 #pragma unroll
 		for (int i = 0; i < KC; i++) {
 			if (i >= nk) continue;
 			const int k = k0 + i;
-			double dmf = 0.0;
-			dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf[i];
-			dmf += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf[i + 1];
-			double F = dmf / jn;
-			double aux = 0.0;
-			if (k < L - 1) {
-				double b = 0.0;
-				b += OPC(TMX_OP_PENALTY_LEFT, k, 0) * q[i + 2];
-				b += OPC(TMX_OP_PENALTY_LEFT, k, 1) * q[i + 3];
-				aux += b * fabs(xd[i + 1]);
-			}
-			if (k > 0) {
-				double b = 0.0;
-				b += OPC(TMX_OP_PENALTY_RIGHT, k, -1) * q[i + 1];
-				b += OPC(TMX_OP_PENALTY_RIGHT, k, 0) * q[i + 2];
-				aux += b * fabs(xd[i]);
-			}
-			F -= aux;
-			if (F != 0.0) F /= idt;
+			const double aux = penalty_row(p.ops, L, k, 0.0, [&](int d) { return q[i + d + 2]; }, fabs(xd[i]), fabs(xd[i + 1]));
+			const double F = tracer_explicit_solve(tracer_rhs_row(p.ops, L, k, mf[i], mf[i + 1], jn, aux), idt);
 			xup[(size_t)TMX_SLAB_Q(L, c, k) * NS + col] = up0[i] - F;
 		}
 	}
@@ -1089,11 +798,8 @@ __global__ __launch_bounds__(64) void k_v_tracers_explicit_walk(KParams p, int n
 // sliding register window -- the four levels k - 1 .. k + 2 of U, V, rho and, for NTR tracers at once, of the column values and
 // mixing-ratio deviations -- so that every operand is loaded once (a segment re-reads the four levels around its ends), the two
 // divisions of a deviation and every interface flux are evaluated once, and the level entering the window is loaded an iteration
-// ahead of its first use.  No LDS, no barrier.  Statement for statement the arithmetic of k_v_tracers_explicit_tile: bit-identical (tested).
-#define OPCL(op, k, off) opsl[(((op) * (L + 1)) + (k)) * TMX_OPW + ((off) + 2)]
-// The operator coefficients and the 1 - eta table come from LDS: the kernel stores to the update instance inside the loop, after which
-// the compiler may not read them through the scalar cache any more (the stores might alias them) -- as vector loads each one waits
-// for every load in flight (s_waitcnt vmcnt(0)), the prefetched level included.
+// ahead of its first use.  No barrier in the walk.  The arithmetic is tracer_edge_flux, penalty_row and tracer_rhs_row (tmx_device.h).
+// The operator coefficients and the 1 - eta table come from LDS (walk_tables_to_lds).
 template <int NTR, bool CLOSED>
 __global__ __launch_bounds__(128) void k_v_tracers_explicit_slide(KParams p, int c0, const double * __restrict__ xin, double * xup, double dt,
 	double ks, const double * __restrict__ xref, int ntile, int xmode, int nseg)
@@ -1102,20 +808,11 @@ __global__ __launch_bounds__(128) void k_v_tracers_explicit_slide(KParams p, int
 	const int L = p.L;
 	const size_t NS = (size_t)p.NS;
 	double * etal = opsl + TMX_OP_COUNT * (L + 1) * TMX_OPW;
-	{
-		const int tid = threadIdx.y * 64 + threadIdx.x;
-		for (int t = tid; t < TMX_OP_COUNT * (L + 1) * TMX_OPW; t += 128) opsl[t] = p.ops[t];
-		if (CLOSED) for (int t = tid; t < 2 * L + 1; t += 128) etal[t] = p.eta[t];
-		__syncthreads();
-	}
+	walk_tables_to_lds<CLOSED>(p, opsl, etal);
+	__syncthreads();
 	constexpr int MM = CLOSED ? 1 : 2;
-	int bx, by;
-	if (!xcd_column_tile(xmode, ntile, (nseg + 1) / 2, bx, by)) return;
-	const int col = (p.quads ? p.quads[bx] : bx) * 64 + threadIdx.x;
-	if (col >= p.ncol) return;
-	const int sg = WAVE_UNIFORM(by * 2 + (int)threadIdx.y);      // the two wavefronts of a workgroup: two segments of the same columns
-	const int seg = (L + nseg - 1) / nseg, k0 = sg * seg, k1 = min(L, k0 + seg);
-	if (sg >= nseg || k0 >= k1) return;
+	int col, k0, k1;
+	if (!walk_segment(p, xmode, ntile, nseg, L, col, k0, k1)) return;
 	const double * w0 = xin + (size_t)TMX_SLAB_W(L, 0) * NS;
 	const double jn = p.g2d[G2_JN * NS + col], je = p.g2d[G2_JE * NS + col];
 	const MetCol mc = met_col(p, col);
@@ -1167,69 +864,21 @@ __global__ __launch_bounds__(128) void k_v_tracers_explicit_slide(KParams p, int
 		// xi_dot (zero at the boundaries) and, with uniform diffusion, rho on interface m
 		double xd_hi = 0.0, re_hi = 0.0;
 		if (m >= 1 && m <= L - 1) {
-			double ue = 0.0, ve = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				const double cc = OPCL(TMX_OP_INTERP_NODE_TO_REDGE, m, off);
-				ue += cc * uw[off + 2];
-				ve += cc * vw[off + 2];
-			}
+			const double ue = edge_sum(opsl, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return uw[off + 2]; });
+			const double ve = edge_sum(opsl, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return vw[off + 2]; });
 			double e0, e1, e2;
 			metric_edge<MM>(p, mc, m, col, e0, e1, e2, etal);
 			xd_hi = e0 * ue + e1 * ve + e2 * wm;
 		}
-		if (ud && m <= L) {
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				re_hi += OPCL(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * rh[off + 2];
-			}
-		}
+		if (ud && m <= L) re_hi = edge_sum(opsl, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return rh[off + 2]; });
 		double res[NTR];
 #pragma unroll
 		for (int t = 0; t < NTR; t++) {
-			double qe = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 1; off++) {
-				const int l = m + off;
-				if (l < 0 || l >= L) continue;
-				qe += OPCL(TMX_OP_INTERP_NODE_TO_REDGE, m, off) * q[t][off + 2];
-			}
-			double mf_hi = (m == 0 || m == L) ? 0.0 : je * qe * xd_hi;
-			if (ud && m > 0 && m < L) {
-				double dq = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 1; off++) {
-					const int l = m + off;
-					if (l < 0 || l >= L) continue;
-					dq += OPCL(TMX_OP_DIFF_NODE_TO_REDGE, m, off) * mr[t][off + 2];
-				}
-				mf_hi -= ks * re_hi * dq;
-			}
-			if (k >= k0) {      // level k: window entries 0, 1, 2 are the levels k - 1, k, k + 1
-				double dmf = 0.0;
-				dmf += OPCL(TMX_OP_DIFF_REDGE_TO_NODE, k, 0) * mf_lo[t];
-				dmf += OPCL(TMX_OP_DIFF_REDGE_TO_NODE, k, 1) * mf_hi;
-				double F = dmf / jn;
-				double aux = 0.0;
-				if (k < L - 1) {
-					double b = 0.0;
-					b += OPCL(TMX_OP_PENALTY_LEFT, k, 0) * q[t][1];
-					b += OPCL(TMX_OP_PENALTY_LEFT, k, 1) * q[t][2];
-					aux += b * fabs(xd_hi);
-				}
-				if (k > 0) {
-					double b = 0.0;
-					b += OPCL(TMX_OP_PENALTY_RIGHT, k, -1) * q[t][0];
-					b += OPCL(TMX_OP_PENALTY_RIGHT, k, 0) * q[t][1];
-					aux += b * fabs(xd_lo);
-				}
-				F -= aux;
-				if (F != 0.0) F /= idt;
-				res[t] = up[t] - F;
+			// window entries 0 .. 3 are the levels m - 2 .. m + 1 = k - 1 .. k + 2
+			const double mf_hi = tracer_edge_flux(opsl, L, m, je, xd_hi, ud, ks, re_hi, [&](int off) { return q[t][off + 2]; }, [&](int off) { return mr[t][off + 2]; });
+			if (k >= k0) {
+				const double aux = penalty_row(opsl, L, k, 0.0, [&](int d) { return q[t][d + 1]; }, fabs(xd_lo), fabs(xd_hi));
+				res[t] = up[t] - tracer_explicit_solve(tracer_rhs_row(opsl, L, k, mf_lo[t], mf_hi, jn, aux), idt);
 			} else res[t] = 0.0;
 			mf_lo[t] = mf_hi;
 			// the window moves up one level
@@ -1254,13 +903,11 @@ __global__ __launch_bounds__(128) void k_v_tracers_explicit_slide(KParams p, int
 	}
 }
 
-#undef OPCL
-
 // UpdateColumnTracers in the fully explicit vertical mode: every stored column, in place on the update instance
 int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) {
 	if (e->nt == 0 || p.ncol == 0) return 0;
 	if (!e->opt_vt_column) {      // level-parallel / column-walking forms; option "vt_column": the one-lane-per-column LDS kernel, for A/B and tests
-		const size_t lds_slide = ((size_t)TMX_OP_COUNT * (p.L + 1) * TMX_OPW + 2 * p.L + 1) * sizeof(double);
+		const size_t lds_slide = walk_lds_bytes(p.L);
 #if TMX_EXP
 		if (e->opt_vt_explicit_v1) {      // the form without LDS staging, for A/B and tests
 			dim3 blk(64, 4), grd(NTILES(e, p), (p.L + 3) / 4);
@@ -1273,9 +920,7 @@ int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * x
 			// default (-1000): segments in pairs (the two wavefronts of a workgroup) until the chip has two wavefronts per SIMD, at least five
 			// levels each -- ne30 L40 on one GPU: 1 350 tiles x 2 (measured: 1 / 2 / 3 / 4 segments 4.27 / 4.08 / 4.28 / 4.20 ms per step of BASELINE
 			// config 4's shape, the LDS-tiled kernel 4.67)
-			int nseg = -e->opt_vt_walk;
-			if (e->opt_vt_walk == -1000) for (nseg = 2; nt_ * nseg < 2048 && p.L / (nseg + 2) >= 5; nseg += 2) { }
-			nseg = std::max(1, std::min(nseg, p.L));
+			const int nseg = walk_segments(e->opt_vt_walk, nt_, p.L, 2048);
 			dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
 			const double ks_ = e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0;
 			const size_t lds = lds_slide;
@@ -1305,36 +950,15 @@ int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * x
 		}
 		return 0;
 	}
-	size_t lds; const int lw = vi_tracers_lanes(p.L, lds);
-	if (!lw) return -1;
-#define LAUNCH_VT(LW_) do { hipFuncSetAttribute((const void *)k_vi_tracers<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-	hipLaunchKernelGGL(k_vi_tracers<LW_>, dim3((p.ncol + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, \
-		(const double *)xup, xup, dt, p.ncol, (const int *)nullptr, (const int *)nullptr, e->d_flag, 1, \
-		e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0, (const double *)e->d_ref); } while (0)
-	if (lw == 64) LAUNCH_VT(64); else LAUNCH_VT(32);
-#undef LAUNCH_VT
-	return 0;
+	return launch_vt_columns(e, p, ColumnSet{ p.ncol, nullptr, nullptr }, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, xup, xup, dt,
+		true, e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0, (const double *)e->d_ref, 64);
 }
 
 // UpdateColumnTracers at the end of StepImplicitTermsExplicitly (VerticalDynamicsFEM.cpp:600-608): the implicit column update
 // of the tracers, on every stored column (the reference loops over all nodes there, :541-542), in place on the update instance
 int tmxk_vi_tracers_all(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) {
 	if (e->nt == 0 || p.ncol == 0) return 0;
-	if (e->opt_vt_rows) {
-		const size_t l2 = vt_rows_lds(p.L);
-		if (l2 <= 160 * 1024) {
-			launch_vt_rows(e, p, p.ncol, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, (const double *)xup, xup, dt, nullptr, nullptr, l2);
-			return 0;
-		}
-	}
-	size_t lds; const int lw = vi_tracers_lanes(p.L, lds);
-	if (!lw) return -1;
-#define LAUNCH_VT(LW_) do { hipFuncSetAttribute((const void *)k_vi_tracers<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-	hipLaunchKernelGGL(k_vi_tracers<LW_>, dim3((p.ncol + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, \
-		(const double *)xup, xup, dt, p.ncol, (const int *)nullptr, (const int *)nullptr, e->d_flag, 0, 0.0, (const double *)nullptr); } while (0)
-	if (lw == 64) LAUNCH_VT(64); else LAUNCH_VT(32);
-#undef LAUNCH_VT
-	return 0;
+	return launch_vt_columns(e, p, ColumnSet{ p.ncol, nullptr, nullptr }, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, xup, xup, dt, false, 0.0, nullptr, 64);
 }
 
 __global__ __launch_bounds__(256) void k_v_filter_tracers(KParams p, int nt, const double * __restrict__ area, double * x) {

@@ -678,11 +678,16 @@ bool hypervis_active(const tmx_engine * e) {
 extern "C" int tmx_v_step_implicit_terms_explicitly(tmx_engine * e, int iinit, int iupd, double dt) {
 	int r; if ((r = check_ready(e)) || (r = check_inst(e, iinit)) || (r = check_inst(e, iupd))) return r;
 	REQUIRE(iinit != iupd && dt != 0.0, TMX_ERR_INVALID, "StepImplicitTermsExplicitly: distinct instances and non-zero dt required");
+	if (e->fully_explicit && (r = check_reference_state(e))) return r;
 	ProfScope ps(e, TMX_K_VI_ASSEMBLE);
 	tmxk_vi_terms_explicit(e, make_params(e), inst(e, iinit), inst(e, iupd), dt, false);
-	if (e->nt > 0)      // UpdateColumnTracers(dt, initial, update, ...) of every column, :600-608
-		REQUIRE(tmxk_vi_tracers_all(e, make_params(e), inst(e, iinit), inst(e, iupd), dt) == 0, TMX_ERR_UNSUPPORTED,
-			"tracer column update: %d levels do not fit the LDS working set", e->L);
+	if (e->nt > 0) {
+		// UpdateColumnTracers(dt, initial, update, ...) of every column, :600-608; in the fully explicit mode it takes its explicit branch
+		// here as everywhere (:3912, :4048: diagonal matrix, xi_dot of the initial column, uniform diffusion of the mixing ratio)
+		const int rt = e->fully_explicit ? tmxk_vi_tracers_explicit(e, make_params(e), inst(e, iinit), inst(e, iupd), dt)
+			: tmxk_vi_tracers_all(e, make_params(e), inst(e, iinit), inst(e, iupd), dt);
+		REQUIRE(rt == 0, TMX_ERR_UNSUPPORTED, "tracer column update: %d levels do not fit the LDS working set", e->L);
+	}
 	return launch_check("v_step_implicit_terms_explicitly");
 }
 // ---------------------------------------------------------------------------------------------

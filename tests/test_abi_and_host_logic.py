@@ -513,6 +513,54 @@ def test_stage_combinations_that_start_from_a_stored_partial_sum():
     assert lib.tmx_debug_program_prefix(99, 0, 0, pairs, terms, 8) == -1
 
 
+def test_walk_segment_counts_of_the_column_walks():
+    """Host logic (no device): the number of segments the three column walks of the vertical kernels split a column into, against the
+    three rules restated (integer division as in C): V.StepExplicit's U,V walk fills 4096 wavefronts over L rows, the tracer walk 2048 over
+    L rows, the walk of the explicitly evaluated implicit terms 2048 over L + 1 rows -- option -1000: segments in pairs while the grid has
+    fewer wavefronts and every segment keeps five rows; -n: n segments; always 1 .. rows."""
+    from tempestmodel_amd import engine as eng
+    lib = eng.load_library()
+    fn = lib.tmx_debug_walk_segments
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_int] * 4
+
+    def rule(option, ntiles, rows, target):
+        nseg = -option
+        if option == -1000:
+            nseg = 2
+            while ntiles * nseg < target and rows // (nseg + 2) >= 5:
+                nseg += 2
+        return max(1, min(nseg, rows))
+
+    def vx_walk(option, ntiles, L):
+        return rule(option, ntiles, L, 4096)
+
+    def vt_explicit_walk(option, ntiles, L):
+        return rule(option, ntiles, L, 2048)
+
+    def vite_walk(option, ntiles, L):
+        return rule(option, ntiles, L + 1, 2048)
+
+    # tile counts 1 .. 5400: the small ones, a stride through the rest, 6, 54, ne30's 1350 and ne60's 5400, and both sides of every count at
+    # which the grid-size rule takes another pair of segments
+    edges = [t // n + d for t in (2048, 4096) for n in range(2, 132, 2) for d in (-1, 0, 1)]
+    tiles = sorted(set(t for t in list(range(1, 70)) + list(range(70, 5401, 37)) + [6, 54, 1350, 5400] + edges if 1 <= t <= 5400))
+    assert tiles[0] == 1 and tiles[-1] == 5400 and {6, 54, 1350, 5400, 1023, 1024, 2048, 2049}.issubset(tiles)
+    seen = set()
+    for ntiles in tiles:
+        for rows in range(3, 131):
+            for option in (-1000, -1, -2, -3, -5, -64):
+                # rows = L for the first two walks, L + 1 for the third (L = rows - 1 >= 2 there; the rule itself takes any rows)
+                want = (vx_walk(option, ntiles, rows), vt_explicit_walk(option, ntiles, rows), vite_walk(option, ntiles, rows - 1))
+                got = (fn(option, ntiles, rows, 4096), fn(option, ntiles, rows, 2048), fn(option, ntiles, rows, 2048))
+                assert got == want, (option, ntiles, rows, got, want)
+                assert all(1 <= n <= rows for n in got)
+                seen.update(got)
+    assert {1, 2, 3, 5, 64}.issubset(seen) and max(seen) == 64      # the sweep reaches the clamp, the forced counts and the grid-size rule's range
+    # the shapes the launchers' comments quote: ne30 (1350 tiles) L40 walks U,V in 4 segments and the tracers in 2
+    assert fn(-1000, 1350, 40, 4096) == 4 and fn(-1000, 1350, 40, 2048) == 2 and fn(-1000, 1350, 41, 2048) == 2
+
+
 def test_lu_flavour_probe_recognises_the_callers_dgbsv():
     """tmx_lu_flavour_from_dgbsv: which band LU does the caller's LAPACK compute?  Handed the C oracle's dgbsv in either mode (a
     restatement that is pinned to the real libraries: test_oracle_vs_reference.py) it must name the mode and set the engine's option; handed
