@@ -183,7 +183,7 @@ def mismatches(e, d, g, want_node, want_tr, want_pr, patches=None):
                            ("PRECT", pr[p][1:-1, 1:-1], want_pr[p])):
             if not np.array_equal(a, b):
                 with np.errstate(invalid="ignore"):
-                    rel = float(np.nanmax(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300) if a.shape == np.shape(b) and np.size(b) else float("nan")
+                    rel = float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300) if a.shape == np.shape(b) and np.size(b) else float("nan")
                 bad.append("patch %d %s: %d of %d entries differ, %d not finite, max relative %.3e"
                            % (p, what, int(np.sum(a != b)), a.size, int(np.sum(~np.isfinite(a))), rel))
     return bad

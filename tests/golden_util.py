@@ -117,14 +117,61 @@ def expand_compact_tracers(d, tag, grid):
     return out
 
 
+_INF = float("inf")
+
+
+def _pair(a, b):
+    """The per-pair work of every comparison helper below: (max |a - b|, max |b|) of two arrays of ONE shape, as plain floats.  A NaN or
+    an infinity anywhere in ``a`` or in ``b`` gives (inf, inf) -- also where both sides hold the same one: nothing on the compared paths
+    stores one by design, and Python's max(0.0, nan) == 0.0 used to turn such a result into an exact match.
+    Unequal shapes raise: ``a - b`` would broadcast a level axis of 1 against L levels without complaint."""
+    a = np.asarray(a); b = np.asarray(b)
+    if a.shape != b.shape:
+        raise ValueError("compared arrays differ in shape: %s against %s" % (a.shape, b.shape))
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        return _INF, _INF
+    return float(np.max(np.abs(a - b))), float(np.max(np.abs(b)))
+
+
+def worse(x, y):
+    """The larger of two error figures; inf as soon as either is NaN or infinite (max(x, y) keeps whichever NaN does not compare
+    against).  For the local ``worst = ...`` folds of the tests."""
+    if not (x == x and y == y) or x == _INF or y == _INF or x == -_INF or y == -_INF:
+        return _INF
+    return y if y > x else x
+
+
+def _fold(pairs, floor=0.0):
+    """max |a - b| over the pairs relative to max |b| over the pairs (absolute where that is not above ``floor`` = 0.0; divided by
+    ``floor`` itself where one is given), inf if any pair is not finite.  Both maxima start at 0.0 and grow by comparison, which on finite
+    data gives the floats the former max() folds gave."""
+    num = den = 0.0
+    for a, b in pairs:
+        n, d = _pair(a, b)
+        num, den = worse(num, n), worse(den, d)
+    if num == _INF or den == _INF:
+        return _INF
+    if floor > 0.0:
+        return num / (den if den > floor else floor)
+    return num / den if den > 0 else num
+
+
+def _same_patches(got, ref):
+    got, ref = list(got), list(ref)
+    if len(got) != len(ref):
+        raise ValueError("compared states differ in their number of patches: %d against %d (slice both sides to compare a subset)" % (len(got), len(ref)))
+    return got, ref
+
+
 def tracer_errors(got, ref):
-    """Max abs difference per tracer over interior nodes, relative to the max abs value of that tracer in ``ref``."""
+    """Max abs difference per tracer over interior nodes, relative to the max abs value of that tracer in ``ref``.  inf for a tracer
+    whose interior holds a NaN or an infinity on either side; another patch count or another shape raises (_pair)."""
+    got, ref = _same_patches(got, ref)
+    for a, b in zip(got, ref):
+        if np.shape(a) != np.shape(b):
+            raise ValueError("compared tracer arrays differ in shape: %s against %s" % (np.shape(a), np.shape(b)))
     nt = ref[0].shape[0]
-    errs = []
-    for c in range(nt):
-        num = max(float(np.max(np.abs(a[c, 1:-1, 1:-1] - b[c, 1:-1, 1:-1]))) for a, b in zip(got, ref))
-        den = max(float(np.max(np.abs(b[c, 1:-1, 1:-1]))) for b in ref)
-        errs.append(num / den if den > 0 else num)
+    errs = [_fold([(a[c, 1:-1, 1:-1], b[c, 1:-1, 1:-1]) for a, b in zip(got, ref)]) for c in range(nt)]
     _report("tracers", errs)
     return errs
 
@@ -147,17 +194,20 @@ def expand_compact(d, tag, grid):
 
 def prognostic_errors(got, ref, interior=True):
     """Max abs difference per variable (U,V,rhotheta,W,rho) over the prognostic slots, relative to the
-    max abs value of that variable in ``ref``."""
+    max abs value of that variable in ``ref``.  inf for a variable whose compared region (its prognostic slot; the interior
+    with ``interior``) holds a NaN or an infinity on either side; the halo ring under ``interior`` and the other slots (node
+    slot 3, interface slots 0, 1, 2, 4) may hold anything.  Another patch count or another shape raises (_pair)."""
+    got, ref = _same_patches(got, ref)
     errs = []
     for c in range(5):
-        m = 0.0; s = 0.0
         loc = 1 if c == 3 else 0
+        pairs = []
         for (gn, ge), (rn, re_) in zip(got, ref):
             a = (ge if loc else gn)[c]; b = (re_ if loc else rn)[c]
             if interior:
                 a = a[1:-1, 1:-1]; b = b[1:-1, 1:-1]
-            m = max(m, float(np.max(np.abs(a - b)))); s = max(s, float(np.max(np.abs(b))))
-        errs.append(m / s if s > 0 else m)
+            pairs.append((a, b))
+        errs.append(_fold(pairs))
     _report("state", errs)
     return errs
 
@@ -173,7 +223,14 @@ def interp_case(d):
 
 
 def interp_rel(x, y):
-    return max(float(np.max(np.abs(x[c] - y[c])) / max(np.max(np.abs(y[c])), 1e-300)) for c in range(x.shape[0]))
+    """Max over the fields of max |x[c] - y[c]| relative to max |y[c]| (at least 1e-300); inf if a field holds a NaN or an infinity
+    on either side, another shape raises (_pair)."""
+    if np.shape(x) != np.shape(y):
+        raise ValueError("compared arrays differ in shape: %s against %s" % (np.shape(x), np.shape(y)))
+    worst = 0.0
+    for c in range(np.shape(x)[0]):
+        worst = worse(worst, _fold([(x[c], y[c])], floor=1e-300))
+    return worst
 
 
 _EXACT_TOL = None

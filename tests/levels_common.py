@@ -216,8 +216,8 @@ def field_distance(got, want, full):
     where the field is identically zero (W through an operator row that picks the top interface, where W = 0)."""
     out = []
     for c in range(len(want)):
-        num, den = float(np.max(np.abs(got[c] - want[c]))), float(np.max(np.abs(full[c])))
-        out.append(num / den if den > 0.0 else num)
+        num, den = gu._pair(got[c], want[c])[0], gu._pair(full[c], full[c])[1]      # inf where a value is not finite; unequal shapes raise
+        out.append(float("inf") if float("inf") in (num, den) else num / den if den > 0.0 else num)
     return out
 
 

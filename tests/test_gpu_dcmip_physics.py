@@ -31,26 +31,25 @@ def _upload(e, d, g, tag):
 
 
 def _check_call(e, d, g, start, call):
-    """The device state after a call against the fixture, == 0.0 everywhere (W and tracers 3+ against the starting state).  A value
-    that is not finite comes back as it is and fails the caller's `== 0.0`: Python's max(0.0, nan) is 0.0, which would let a NaN result pass."""
+    """The device state after a call against the fixture, == 0.0 everywhere (W and tracers 3+ against the starting state).  Every pair
+    goes through golden_util's own per-pair function: a value that is not finite, on either side, makes the result inf and fails the
+    caller's `== 0.0` (Python's max(0.0, nan) is 0.0, which would let a NaN result pass), and a pair of unequal shapes raises."""
     got, gt = e.download_state(0), e.download_tracers(0)
     prect = e.download_precipitation(reset=True)
     worst = 0.0
 
-    def fold(worst, diff):
-        m = float(np.max(diff))
-        return m if not np.isfinite(m) or m > worst else worst      # (inf stays: nothing compares greater)
+    def fold(worst, a, b):
+        return gu.worse(worst, gu._pair(a, b)[0])
     for P in g.patches:
         p = P.index
         n, w = got[p]
-        ref_n = dc.decode_after(d, start, call, p, "node")
-        worst = fold(worst, np.abs(n[[0, 1, 2, 4], 1:-1, 1:-1] - ref_n))
-        worst = fold(worst, np.abs(w[3, 1:-1, 1:-1] - d["state/%s/p%d/redge" % (start, p)]))
+        worst = fold(worst, n[[0, 1, 2, 4], 1:-1, 1:-1], dc.decode_after(d, start, call, p, "node"))
+        worst = fold(worst, w[3, 1:-1, 1:-1], d["state/%s/p%d/redge" % (start, p)])
         t = gt[p][:, 1:-1, 1:-1]
-        worst = fold(worst, np.abs(t[:3] - dc.decode_after(d, start, call, p, "tracers")))
+        worst = fold(worst, t[:3], dc.decode_after(d, start, call, p, "tracers"))
         if t.shape[0] > 3:
-            worst = fold(worst, np.abs(t[3:] - d["state/%s/p%d/tracers" % (start, p)][3:]))
-        worst = fold(worst, np.abs(prect[p][1:-1, 1:-1] - d["prect/%s/p%d" % (call, p)][1:-1, 1:-1]))
+            worst = fold(worst, t[3:], d["state/%s/p%d/tracers" % (start, p)][3:])
+        worst = fold(worst, prect[p][1:-1, 1:-1], d["prect/%s/p%d" % (call, p)][1:-1, 1:-1])
     return worst
 
 
@@ -96,7 +95,7 @@ def test_tropical_cyclone_steps_with_dcmip_physics(pbl, prec):
                 base = np.ascontiguousarray(d["state/warm/p%d/%s" % (p, what)])
                 ref = np.bitwise_xor(base.view(np.uint64), s["xor/pbl%d_prec%d_step3/p%d/%s" % (pbl, prec, p, what)]).view(np.float64)
                 have = {"node": got[p][0][[0, 1, 2, 4], 1:-1, 1:-1], "redge": got[p][1][3, 1:-1, 1:-1], "tracers": gt[p][:, 1:-1, 1:-1]}[what]
-                worst = max(worst, float(np.max(np.abs(have - ref)) / max(float(np.max(np.abs(ref))), 1e-300)))
+                worst = gu.worse(worst, gu._fold([(have, ref)], floor=1e-300))
         print("steps pbl %d prec %d: max relative difference vs reference %.3e" % (pbl, prec, worst))
         assert worst <= gu.exact_tolerance(), worst
     finally:

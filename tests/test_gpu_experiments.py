@@ -28,7 +28,8 @@ def test_mfma_contractions_agree_to_rounding(monkeypatch):
             e.step_ars343(dt)
             e.sync()
             errs = gu.prognostic_errors(e.download_state(0), o.get_state(0))
-            worst = max(worst, max(errs))
+            for v in errs:
+                worst = gu.worse(worst, v)
             assert max(errs[c] for c in (0, 1, 2, 4)) < 1e-13 and errs[3] < 1e-11, errs      # W amplifies last-bit changes
         print("MFMA contractions, 3 steps vs oracle:", errs)
         assert worst > 0.0          # it really is a different arithmetic (otherwise the opt-in would be pointless)

@@ -99,8 +99,9 @@ def test_restart_image_is_the_uploaded_arrays(ne, L, nt):
             assert _halo_is_zero(node) and _halo_is_zero(redge) and (nt == 0 or _halo_is_zero(trc)), P.index
             assert not redge[[2, 4]].any(), P.index
             assert _interior_equal(node[3], dn[3]) and _interior_equal(redge[[0, 1]], de[[0, 1]]), P.index
-            worst = max(worst, _dot_bound(e2n, ue[3][1:-1, 1:-1], node[3][1:-1, 1:-1]),
-                        _dot_bound(n2e, un[0][1:-1, 1:-1], redge[0][1:-1, 1:-1]), _dot_bound(n2e, un[1][1:-1, 1:-1], redge[1][1:-1, 1:-1]))
+            for bound in (_dot_bound(e2n, ue[3][1:-1, 1:-1], node[3][1:-1, 1:-1]), _dot_bound(n2e, un[0][1:-1, 1:-1], redge[0][1:-1, 1:-1]),
+                          _dot_bound(n2e, un[1][1:-1, 1:-1], redge[1][1:-1, 1:-1])):
+                worst = gu.worse(worst, bound)      # (a NaN bound becomes inf: max(worst, nan) would drop it)
         print("image ne%d L%d nt%d: derived arrays within %.3f of the gamma_4 bound" % (ne, L, nt, worst))
         assert worst <= 1.0
         # unpack, another instance: the patches in DESCENDING order, so that a lane that runs past its patch's last column damages a
@@ -169,7 +170,7 @@ def test_restart_image_carries_the_tracked_surface_slots():
         assert max(gu.prognostic_errors(b, a)) == 0.0
         for (an, ae), (bn, be) in zip(a, b):
             assert np.array_equal(ae[[2, 4], 1:-1, 1:-1, 0], be[[2, 4], 1:-1, 1:-1, 0])
-        assert max(gu.prognostic_errors(a, down)) > 1e-6      # the two steps moved the state
+        assert 1e-6 < max(gu.prognostic_errors(a, down)) < float("inf")      # the two steps moved the state
     finally:
         e.close()
         if e2 is not None:
@@ -255,10 +256,13 @@ def test_output_interpolation_vs_oracle_and_long_double(ne, L, npatch, case, ntr
                         d_dev, d_orc = lc.field_distance(got, want, full), lc.field_distance(orc, want, full)
                         print("interp %s npts %d nreta %d only %d ref %d prim %d: ulps vs oracle %s; vs long double: device %s oracle %s" % (
                             case, npts, nreta, only, inc, prim, ulps, ["%.1e" % v for v in d_dev], ["%.1e" % v for v in d_orc]))
-                        worst_ulps, worst_dev, worst_orc = max(worst_ulps, *ulps), max(worst_dev, *d_dev), max(worst_orc, *d_orc)
+                        for v in ulps:
+                            worst_ulps = gu.worse(worst_ulps, v)
+                        for v, w in zip(d_dev, d_orc):
+                            worst_dev, worst_orc = gu.worse(worst_dev, v), gu.worse(worst_orc, w)
                         assert np.array_equal(got, orc), (npts, nreta, only, inc, prim, ulps)
                         for c in range(5):
-                            assert d_dev[c] <= max(2.0 * d_orc[c], 8.0 * EPS), (npts, nreta, only, inc, prim, c, d_dev[c], d_orc[c])
+                            assert np.isfinite(d_orc[c]) and d_dev[c] <= max(2.0 * d_orc[c], 8.0 * EPS), (npts, nreta, only, inc, prim, c, d_dev[c], d_orc[c])
                         if nreta == 4:
                             assert not got[:, 2].any() and np.isfinite(got).all()
                         if only == 1:
@@ -272,7 +276,7 @@ def test_output_interpolation_vs_oracle_and_long_double(ne, L, npatch, case, ntr
                         print("interp %s npts %d nreta %d tracers: ulps vs oracle %s; vs long double: device %s oracle %s" % (
                             case, npts, nreta, _ulps(got, orc), ["%.1e" % v for v in d_dev], ["%.1e" % v for v in d_orc]))
                         assert np.array_equal(got, orc), (npts, nreta)
-                        assert all(d_dev[c] <= max(2.0 * d_orc[c], 8.0 * EPS) for c in range(ntr)), (npts, nreta, d_dev, d_orc)
+                        assert all(np.isfinite(d_orc[c]) and d_dev[c] <= max(2.0 * d_orc[c], 8.0 * EPS) for c in range(ntr)), (npts, nreta, d_dev, d_orc)
                         assert got[:, 0].any() and (nreta == 1 or not got[:, 2].any())
                 finally:
                     e.interp_destroy(plan)

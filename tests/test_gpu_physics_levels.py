@@ -124,7 +124,7 @@ def test_held_suarez_kernels_vs_oracle(L):
 
     for variant, pinned, steps in (("a", True, 0), ("b", False, 0), ("c", True, 1)):
         want = oracle(pinned, steps)
-        assert max(gu.prognostic_errors(want, st)) > 1e-6      # the forcing did something
+        assert 1e-6 < max(gu.prognostic_errors(want, st)) < float("inf")      # the forcing did something
         e = Engine(g, options={"unique_layout": 1 if variant == "c" else 0})
         try:
             e.set_physics_inputs(ps if pinned else None)

@@ -35,7 +35,7 @@ def test_moist_supercell_rains_and_splits_the_rain_loop_unevenly(L):
         o.kessler(0, dt, zl, pr); o.kessler(0, dt, zl, pr)
         assert _finite(o.get_state(0), o.get_tracers(0)), (L, dt)
         assert max(float(p[1:-1, 1:-1].max()) for p in pr) > 0.0, (L, dt)
-        assert max(gu.prognostic_errors(o.get_state(0), st)) > 1e-3, (L, dt)      # the call did something to the state
+        assert 1e-3 < max(gu.prognostic_errors(o.get_state(0), st)) < float("inf"), (L, dt)      # the call did something to the state
         n = lc.kessler_subcycles(g, st, tr, dt)
         distinct = max(len(set(n[i:i + 64].tolist())) for i in range(0, len(n) - 63, 64))
         print("L %d dt %g: sub-cycle counts %d..%d, %.0f %% of the columns above 1, up to %d distinct in a group of 64" % (L, dt, n.min(), n.max(), 100.0 * np.mean(n > 1), distinct))
@@ -97,7 +97,7 @@ def test_interp_state_is_away_from_the_reference_state_and_w_is_not_zero(ne, L, 
         d = np.asarray(P.geom["deriv_r_redge"])[..., 2]
         for a in range(1, P.na - 1, 4):
             for b in range(1, P.nb - 1, 4):
-                spread = max(spread, float(np.max(np.abs(d[a:a + 4, b:b + 4] / d[a, b] - 1.0))))
+                spread = gu.worse(spread, float(np.max(np.abs(d[a:a + 4, b:b + 4] / d[a, b] - 1.0))))
     print("%s ne%d L%d: d_xi R differs by up to %.2e relative inside an element" % (case, ne, L, spread))
     assert spread > 1e-6
 

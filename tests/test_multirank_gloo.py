@@ -116,7 +116,8 @@ def _worker(rank, world, port, q):
             ref = np.concatenate([wn[0, i, j], wn[1, i, j], wn[2, i, j], wn[4, i, j], we[3, i, j]])
             scale = np.array([np.abs(wn[0]).max()] * L + [np.abs(wn[1]).max()] * L + [np.abs(wn[2]).max()] * L
                              + [np.abs(wn[4]).max()] * L + [max(np.abs(we[3]).max(), 1e-300)] * (L + 1))
-            worst = max(worst, float(np.max(np.abs(res[m] - ref) / scale)))
+            x = float(np.max(np.abs(res[m] - ref) / scale))
+            worst = x if not np.isfinite(x) or x > worst else worst      # (max(worst, nan) would drop a NaN; one that is kept fails `== 0.0`)
     e.close()
     q.put((rank, worst, len(send), len(recv)))
     dist.barrier()
