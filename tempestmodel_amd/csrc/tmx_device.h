@@ -351,6 +351,112 @@ __device__ __forceinline__ double penalty_row(const double * ops, int L, int k, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Element-local operators of ApplyScalarHyperdiffusion / ApplyVectorHyperdiffusion / ComputeCurlAndDiv (HorizontalDynamicsFEM.cpp:1867-2414,
+// GridPatchCSGLL.cpp:1132-1305), stated once for the kernels that evaluate them: the hyperviscosity passes (k_hypervis,
+// k_hypervis_tracers; k_hypervis_block: the pointwise statements, its contractions stay under its `held` predicate), the uniform diffusion
+// (k_uniform_diffusion, k_ref_diffusion_terms) and the tracers' diffusive flux (k_h_tracers<UD>).  k_h_walk<UD> keeps its own copy of
+// k_uniform_diffusion's statements and k_hv_walk k_hypervis's: the registers of the one are counted, the other ran 1.5 % longer per launch
+// with the shared ones (profiles/viscosity_operators_statement_list.md).
+// An element's 16 nodes lie in one run of an LDS row, node (i, j) at eb + 4 i + j.  Where the operands come from, barriers, prefetches and
+// stores stay with each kernel.  Operand order as in the reference; nothing is contracted (-ffp-contract=off).
+// ElPos: the thread's node (i, j), its element's base offset eb in an LDS row, and the row positions the contractions run over: la[t] = node
+// (t, j) along alpha, lb[t] = node (i, t) along beta.  They are formed by the caller (el_pos, from its lane), not inside the contractions:
+// there the compiler knows which bits of the lane each term holds and keeps one address per access, as in the hand-written loops; formed
+// from i, j, eb inside the contractions, the addresses come out as chains of base + constant (k_hv_walk, when tried: 7 registers, 4 bytes of scratch more).
+struct ElPos { int i, j, eb, la[4], lb[4]; };
+__device__ __forceinline__ ElPos el_pos(int lane, int eb) {
+	ElPos e;
+	e.i = (lane & 15) >> 2; e.j = lane & 3; e.eb = eb;
+#pragma unroll
+	for (int t = 0; t < 4; t++) { e.la[t] = eb + 4 * t + e.j; e.lb[t] = eb + 4 * e.i + t; }
+	return e;
+}
+struct ElPair { double a, b; };
+
+// da[n] = d/dalpha of row ra[n], db[n] = d/dbeta of row rb[n]: contraction with the derivative matrix sD, then the patch's 1 / element spacing
+template <int N, int NR, int RL>
+__device__ __forceinline__ void el_deriv(double (&s)[NR][RL], const double (&sD)[16], const ElPos & e, const int (&ra)[N], const int (&rb)[N],
+	double ida, double idb, double (&da)[N], double (&db)[N])
+{
+#pragma unroll
+	for (int n = 0; n < N; n++) da[n] = db[n] = 0.0;
+#pragma unroll
+	for (int t = 0; t < 4; t++) {
+		const double Da = sD[t * 4 + e.i], Db = sD[t * 4 + e.j];
+#pragma unroll
+		for (int n = 0; n < N; n++) { da[n] += s[ra[n]][e.la[t]] * Da; db[n] += s[rb[n]][e.lb[t]] * Db; }
+	}
+#pragma unroll
+	for (int n = 0; n < N; n++) { da[n] *= ida; db[n] *= idb; }
+}
+// Contraction with the stiffness matrix sS: the weak divergence of NP flux pairs (alpha component in row pa[n], beta in pb[n]: its two halves
+// in ua[n], ub[n]), the weak gradient of NG scalar rows g[n] (ga[n], gb[n]), and both in one pass
+template <int NP, int NR, int RL>
+__device__ __forceinline__ void el_wdiv(double (&s)[NR][RL], const double (&sS)[16], const ElPos & e, const int (&pa)[NP], const int (&pb)[NP],
+	double ida, double idb, double (&ua)[NP], double (&ub)[NP])
+{
+#pragma unroll
+	for (int n = 0; n < NP; n++) ua[n] = ub[n] = 0.0;
+#pragma unroll
+	for (int t = 0; t < 4; t++) {
+		const double Sa = sS[e.i * 4 + t], Sb = sS[e.j * 4 + t];
+#pragma unroll
+		for (int n = 0; n < NP; n++) { ua[n] += s[pa[n]][e.la[t]] * Sa; ub[n] += s[pb[n]][e.lb[t]] * Sb; }
+	}
+#pragma unroll
+	for (int n = 0; n < NP; n++) { ua[n] *= ida; ub[n] *= idb; }
+}
+template <int NG, int NR, int RL>
+__device__ __forceinline__ void el_wgrad(double (&s)[NR][RL], const double (&sS)[16], const ElPos & e, const int (&g)[NG], double ida, double idb,
+	double (&ga)[NG], double (&gb)[NG])
+{
+#pragma unroll
+	for (int n = 0; n < NG; n++) ga[n] = gb[n] = 0.0;
+#pragma unroll
+	for (int t = 0; t < 4; t++) {
+		const double Sa = sS[e.i * 4 + t], Sb = sS[e.j * 4 + t];
+#pragma unroll
+		for (int n = 0; n < NG; n++) { ga[n] -= Sa * s[g[n]][e.la[t]]; gb[n] -= Sb * s[g[n]][e.lb[t]]; }
+	}
+#pragma unroll
+	for (int n = 0; n < NG; n++) { ga[n] *= ida; gb[n] *= idb; }
+}
+template <int NP, int NG, int NR, int RL>
+__device__ __forceinline__ void el_stiff(double (&s)[NR][RL], const double (&sS)[16], const ElPos & e, const int (&pa)[NP], const int (&pb)[NP], const int (&g)[NG],
+	double ida, double idb, double (&ua)[NP], double (&ub)[NP], double (&ga)[NG], double (&gb)[NG])
+{
+#pragma unroll
+	for (int n = 0; n < NP; n++) ua[n] = ub[n] = 0.0;
+#pragma unroll
+	for (int n = 0; n < NG; n++) ga[n] = gb[n] = 0.0;
+#pragma unroll
+	for (int t = 0; t < 4; t++) {
+		const double Sa = sS[e.i * 4 + t], Sb = sS[e.j * 4 + t];
+#pragma unroll
+		for (int n = 0; n < NP; n++) { ua[n] += s[pa[n]][e.la[t]] * Sa; ub[n] += s[pb[n]][e.lb[t]] * Sb; }
+#pragma unroll
+		for (int n = 0; n < NG; n++) { ga[n] -= Sa * s[g[n]][e.la[t]]; gb[n] -= Sb * s[g[n]][e.lb[t]]; }
+	}
+#pragma unroll
+	for (int n = 0; n < NP; n++) { ua[n] *= ida; ub[n] *= idb; }
+#pragma unroll
+	for (int n = 0; n < NG; n++) { ga[n] *= ida; gb[n] *= idb; }
+}
+// The pointwise statements between the passes.  Contravariant components times a Jacobian: of a gradient (the scalar Laplacian's flux), of (U, V)
+__device__ __forceinline__ ElPair el_flux(double J, double c2a0, double c2a1, double c2b1, double da, double db) {
+	return { J * (c2a0 * da + c2a1 * db), J * (c2a1 * da + c2b1 * db) };
+}
+// divergence (a) and curl (b) from d_alpha (J u^alpha), d_beta (J u^beta), d_alpha u_beta, d_beta u_alpha
+__device__ __forceinline__ ElPair el_div_curl(double dajua, double dbjub, double daub, double dbua, double invJ2) {
+	return { (dajua + dbjub) * invJ2, (daub - dbua) * invJ2 };
+}
+// increments of (U, V) from the weak gradients of the divergence (dad, dbd) and of the curl (dac, dbc)
+__device__ __forceinline__ ElPair el_vector_update(double nd, double nv, double j2d, double c2a0, double c2a1, double c2b1, double dad, double dbd, double dac, double dbc) {
+	return { nd * dad - nv * j2d * (c2a1 * dac + c2b1 * dbc), nd * dbd + nv * j2d * (c2a0 * dac + c2a1 * dbc) };
+}
+__device__ __forceinline__ double el_scalar_update(double b, double dt, double invJ, double nu, double ua, double ub) { return b - dt * invJ * nu * (ua + ub); }
+
+// ---------------------------------------------------------------------------------------------
 // UpdateColumnTracers (VerticalDynamicsFEM.cpp:3943-4233): the right-hand side of a tracer's column update, stated once for every
 // kernel of tmx_k_vertical.hip that evaluates it -- whichever way it spreads the work and wherever it keeps the operands.
 // Tracer flux through interface m (:4092-4140): J_e x (tracer density on the interface) x xi_dot, none through the boundaries; with

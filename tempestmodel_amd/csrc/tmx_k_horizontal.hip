@@ -652,6 +652,7 @@ __global__ __launch_bounds__(256) void k_h_tracers(KParams p, int nt, const doub
 	}
 	s[ty][3][lane] = ar;
 	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
+	const ElPos ep = el_pos(lane, eb);      // (for el_deriv under UD alone: the kept loops below indexed through it move the UD = false instantiations' code)
 	for (int c = 0; c < nt; c++) {
 		const size_t so = (size_t)TMX_SLAB_Q(L, c, kc) * NS;
 		const double qv = act ? ldu(xin + so, cb) : 0.0;
@@ -661,15 +662,10 @@ __global__ __launch_bounds__(256) void k_h_tracers(KParams p, int nt, const doub
 			__syncthreads();
 			s[ty][4][lane] = qv / rho;
 			__syncthreads();
-			double daq = 0.0, dbq = 0.0;
-#pragma unroll
-			for (int t = 0; t < 4; t++) {
-				daq += s[ty][4][eb + 4 * t + j] * sD[t * 4 + i];
-				dbq += s[ty][4][eb + 4 * i + t] * sD[t * 4 + j];
-			}
-			daq *= ida; dbq *= idb;
-			const double cdaq = dc2a0 * daq + dc2a1 * dbq;
-			const double cdbq = dc2a1 * daq + dc2b1 * dbq;
+			double daq[1], dbq[1];
+			el_deriv(s[ty], sD, ep, { 4 }, { 4 }, ida, idb, daq, dbq);
+			const double cdaq = dc2a0 * daq[0] + dc2a1 * dbq[0];
+			const double cdbq = dc2a1 * daq[0] + dc2b1 * dbq[0];
 			taf -= ks * djn * rho * cdaq;
 			tbf -= ks * djn * rho * cdbq;
 		}
@@ -736,7 +732,7 @@ __global__ __launch_bounds__(256) void k_hypervis_tracers(KParams p, int nt, con
 		if (filter) ar = ldu(area + (size_t)kc * NS, cb);
 	}
 	s[ty][3][lane] = ar;
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
+	const ElPos ep = el_pos(lane, lane & 48);
 	for (int c = 0; c < nt; c++) {
 		const size_t so = (size_t)TMX_SLAB_Q(L, c, kc) * NS;
 		const double psi = act ? ldu(xsrc + so, cb) : 0.0;
@@ -744,24 +740,13 @@ __global__ __launch_bounds__(256) void k_hypervis_tracers(KParams p, int nt, con
 		__syncthreads();
 		s[ty][0][lane] = psi;
 		__syncthreads();
-		double da = 0.0, db = 0.0;
-#pragma unroll
-		for (int t = 0; t < 4; t++) {
-			da += s[ty][0][eb + 4 * t + j] * sD[t * 4 + i];
-			db += s[ty][0][eb + 4 * i + t] * sD[t * 4 + j];
-		}
-		da *= ida; db *= idb;
-		s[ty][1][lane] = jn * (c2a0 * da + c2a1 * db);
-		s[ty][2][lane] = jn * (c2a1 * da + c2b1 * db);
+		double da[1], db[1], ua[1], ub[1];
+		el_deriv(s[ty], sD, ep, { 0 }, { 0 }, ida, idb, da, db);
+		const ElPair f = el_flux(jn, c2a0, c2a1, c2b1, da[0], db[0]);
+		s[ty][1][lane] = f.a; s[ty][2][lane] = f.b;
 		__syncthreads();
-		double ua = 0.0, ub = 0.0;
-#pragma unroll
-		for (int t = 0; t < 4; t++) {
-			ua += s[ty][1][eb + 4 * t + j] * sS[i * 4 + t];
-			ub += s[ty][2][eb + 4 * i + t] * sS[j * 4 + t];
-		}
-		ua *= ida; ub *= idb;
-		double out = bv - dt * (1.0 / jn) * nu * (ua + ub);
+		el_wdiv(s[ty], sS, ep, { 1 }, { 2 }, ida, idb, ua, ub);
+		double out = el_scalar_update(bv, dt, 1.0 / jn, nu, ua[0], ub[0]);
 		if (filter) {
 			__syncthreads();
 			s[ty][0][lane] = out;
@@ -769,8 +754,8 @@ __global__ __launch_bounds__(256) void k_hypervis_tracers(KParams p, int nt, con
 			double total = 0.0, nonneg = 0.0;
 #pragma unroll
 			for (int n = 0; n < 16; n++) {
-				const double qq = s[ty][0][eb + n];
-				const double pm = qq * s[ty][3][eb + n];
+				const double qq = s[ty][0][ep.eb + n];
+				const double pm = qq * s[ty][3][ep.eb + n];
 				total += pm;
 				if (qq >= 0.0) nonneg += pm;
 			}
@@ -786,21 +771,6 @@ void tmxk_hypervis_tracers(tmx_engine * e, const KParams & p, const double * xsr
 	hipLaunchKernelGGL(k_hypervis_tracers, grd, blk, 0, e->stream, p, e->nt, (const double *)e->d_area, xsrc, xbase, xout, dt, nu, filter, scale);
 }
 
-// VerticalDynamicsFEM::UpdateColumnTracers (VerticalDynamicsFEM.cpp:3783-4282), implicit mode, vertical order 1:
-// one lane per unique column.  The tridiagonal matrix (kl = ku = 1) is kept in LAPACK band storage
-// AB(i, j) = sm[(j * 4 + 2 + i - j)] and factorised / solved with the dgbtf2 / dgbtrs loops (first-maximum
-// pivoting, column-oriented back substitution) -- the restatement oracle/tmx_oracle.c:orc_dgbsv pins against
-// LAPACK -- once per tracer on a fresh copy, which is what dgbtrf + dgbtrs per tracer compute.
-// xin: initial instance (U, V, tracer densities), w0: W of the initial column [L+1][NS] (a saved copy when the step
-// runs in place and the state kernel has already overwritten it), xup: update instance (updated W; receives the tracers),
-// xbase: instance holding the tracer values the update is subtracted from (the update instance itself in the
-// reference; the initial instance when the preceding CopyData was fused away).
-// expl (fully explicit vertical mode, :3910-3912, :4047-4063, :4117-4141, :4166-4170, :4193): every stored column is
-// advanced on its own (ucol == udep == nullptr; the update instance has not been through the DSS yet), the matrix is
-// the diagonal 1/dt (dgbtrs then is one division per level), xi_dot comes from the initial W for both uses, there
-// is no velocity correction, and with ks != 0 the mass flux carries the uniform diffusion of q / rho - (q / rho)_ref.
-// LW = columns per workgroup (the lane stride of the LDS arrays): 64, or 32 when (8L + 2) x 512 bytes exceed the 160 KB of a
-// CU (L >= 40, e.g. the 40 levels of the DCMIP2016 supercell) -- half-filled wavefronts, twice the workgroups.
 // ---------------------------------------------------------------------------------------------
 // Hyperviscosity pass: scalar Laplacian of rho*theta, W, rho and vector Laplacian of (U,V)
 // (ApplyScalarHyperdiffusion / ApplyVectorHyperdiffusion / ComputeCurlAndDiv,
@@ -912,7 +882,6 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 	__shared__ double xs[BLK ? 5 : 1][BLK ? 256 : 1];
 	const int lane = tile_lane<UQ>(), ty = WAVE_UNIFORM(threadIdx.y);
 	if (lane < 16) { sDw[ty][lane] = p.dx[lane]; sSw[ty][lane] = p.stiff[lane]; }
-	const double * sD = sDw[ty], * sS = sSw[ty];
 	const int lp = lds_pos<UQ>(lane);
 	const int L = p.L;
 	const size_t NS = (size_t)p.NS;
@@ -931,7 +900,7 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 	const bool here = UQ ? (uc >= 0) : (col < p.ncol);
 	const bool actw = (kk <= L) && here;     // interface level (W)
 	const bool actn = (kk < L) && here;      // model level (U,V,rho*theta,rho)
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lds_pos<UQ>(lane & 48);
+	const ElPos ep = el_pos(lane, lds_pos<UQ>(lane & 48));
 
 	double psiT = 0, psiR = 0, psiW = 0, ua = 0, ub = 0;
 	double c2a0 = 0, c2a1 = 0, c2b1 = 0, j2d = 1, jn = 1, je = 1;
@@ -969,65 +938,43 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 			psiW = o[0];
 		}
 	}
-	const double cua = c2a0 * ua + c2a1 * ub;
-	const double cub = c2a1 * ua + c2b1 * ub;
+	const ElPair ju = el_flux(j2d, c2a0, c2a1, c2b1, ua, ub);
 	s[ty][0][lp] = psiT; s[ty][1][lp] = psiR; s[ty][2][lp] = psiW;
 	s[ty][3][lp] = ua;   s[ty][4][lp] = ub;
-	s[ty][5][lp] = j2d * cua; s[ty][6][lp] = j2d * cub;
+	s[ty][5][lp] = ju.a; s[ty][6][lp] = ju.b;
 	wave_sync();
 
-	double daT = 0, dbT = 0, daR = 0, dbR = 0, daW = 0, dbW = 0, daub = 0, dbua = 0, dajua = 0, dbjub = 0;
-#pragma unroll
-	for (int t = 0; t < 4; t++) {
-		const int la = eb + 4 * t + j, lb = eb + 4 * i + t;
-		const double Da = sD[t * 4 + i], Db = sD[t * 4 + j];
-		daT += s[ty][0][la] * Da; dbT += s[ty][0][lb] * Db;
-		daR += s[ty][1][la] * Da; dbR += s[ty][1][lb] * Db;
-		daW += s[ty][2][la] * Da; dbW += s[ty][2][lb] * Db;
-		daub += s[ty][4][la] * Da; dbua += s[ty][3][lb] * Db;
-		dajua += s[ty][5][la] * Da; dbjub += s[ty][6][lb] * Db;
-	}
+	// gradients of rho*theta, rho, W; d_alpha U_beta, d_beta U_alpha; d_alpha (J U^alpha), d_beta (J U^beta)
 	const double ida = p.g2d[G2_IDA * NS + col], idb = p.g2d[G2_IDB * NS + col];
+	double da[5], db[5];
+	el_deriv(s[ty], sDw[ty], ep, { 0, 1, 2, 4, 5 }, { 0, 1, 2, 3, 6 }, ida, idb, da, db);
 	const double nsc = scale ? p.g2d[G2_NUS * NS + col] : 1.0;
 	const double nu_s = nu_s_in * nsc, nu_d = nu_d_in * nsc, nu_v = nu_v_in * nsc;
-	daT *= ida; dbT *= idb; daR *= ida; dbR *= idb; daW *= ida; dbW *= idb;
-	daub *= ida; dbua *= idb; dajua *= ida; dbjub *= idb;
-	const double invJ2 = 1.0 / j2d;
-	const double dv = (dajua + dbjub) * invJ2, cl = (daub - dbua) * invJ2;
+	const ElPair fT = el_flux(jn, c2a0, c2a1, c2b1, da[0], db[0]), fR = el_flux(jn, c2a0, c2a1, c2b1, da[1], db[1]), fW = el_flux(je, c2a0, c2a1, c2b1, da[2], db[2]);
+	const ElPair dc = el_div_curl(da[4], db[4], da[3], db[3], 1.0 / j2d);
 	// what the thread does with its results (seam_store): loaded here, behind the first contraction, used at the end
 	const int sdst = UQ ? (BLK ? p.b_sdst[col] : p.t_sdst[col]) : 0, sred = UQ ? (BLK ? p.b_sred[col] : p.t_sred[col]) : 0;
 	wave_sync();
-	s[ty][0][lp] = jn * (c2a0 * daT + c2a1 * dbT); s[ty][1][lp] = jn * (c2a1 * daT + c2b1 * dbT);
-	s[ty][2][lp] = jn * (c2a0 * daR + c2a1 * dbR); s[ty][3][lp] = jn * (c2a1 * daR + c2b1 * dbR);
-	s[ty][4][lp] = je * (c2a0 * daW + c2a1 * dbW); s[ty][5][lp] = je * (c2a1 * daW + c2b1 * dbW);
-	s[ty][6][lp] = dv; s[ty][7][lp] = cl;
+	s[ty][0][lp] = fT.a; s[ty][1][lp] = fT.b;
+	s[ty][2][lp] = fR.a; s[ty][3][lp] = fR.b;
+	s[ty][4][lp] = fW.a; s[ty][5][lp] = fW.b;
+	s[ty][6][lp] = dc.a; s[ty][7][lp] = dc.b;
 	wave_sync();
 	if (!BLK && !actw) return;      // (BLK: padding lanes stay for the exchange below -- a whole padding wavefront must reach the barrier its block's others wait at)
 
-	double uaT = 0, ubT = 0, uaR = 0, ubR = 0, uaW = 0, ubW = 0, dad = 0, dbd = 0, dac = 0, dbc = 0;
-#pragma unroll
-	for (int t = 0; t < 4; t++) {
-		const int la = eb + 4 * t + j, lb = eb + 4 * i + t;
-		const double Sa = sS[i * 4 + t], Sb = sS[j * 4 + t];
-		uaT += s[ty][0][la] * Sa; ubT += s[ty][1][lb] * Sb;
-		uaR += s[ty][2][la] * Sa; ubR += s[ty][3][lb] * Sb;
-		uaW += s[ty][4][la] * Sa; ubW += s[ty][5][lb] * Sb;
-		dad -= Sa * s[ty][6][la]; dbd -= Sb * s[ty][6][lb];
-		dac -= Sa * s[ty][7][la]; dbc -= Sb * s[ty][7][lb];
-	}
-	uaT *= ida; ubT *= idb; uaR *= ida; ubR *= idb; uaW *= ida; ubW *= idb;
-	dad *= ida; dbd *= idb; dac *= ida; dbc *= idb;
+	// weak divergences of the three fluxes (T, R, W), weak gradients of divergence and curl
+	double wa[3], wb[3], ga[2], gb[2];
+	el_stiff(s[ty], sSw[ty], ep, { 0, 2, 4 }, { 1, 3, 5 }, { 6, 7 }, ida, idb, wa, wb, ga, gb);
 
-	const double oW = bW - dt * (1.0 / je) * nu_s * (uaW + ubW);
+	const double oW = el_scalar_update(bW, dt, 1.0 / je, nu_s, wa[2], wb[2]);
 	double oT = 0, oR = 0, oU = 0, oV = 0;
 	if (actn) {
 		const double invJ = 1.0 / jn;
-		oT = bT - dt * invJ * nu_s * (uaT + ubT);
-		oR = bR - dt * invJ * nu_s * (uaR + ubR);
-		const double upa = nu_d * dad - nu_v * j2d * (c2a1 * dac + c2b1 * dbc);
-		const double upb = nu_d * dbd + nu_v * j2d * (c2a0 * dac + c2a1 * dbc);
-		oU = bU - dt * upa;
-		oV = bV - dt * upb;
+		oT = el_scalar_update(bT, dt, invJ, nu_s, wa[0], wb[0]);
+		oR = el_scalar_update(bR, dt, invJ, nu_s, wa[1], wb[1]);
+		const ElPair up = el_vector_update(nu_d, nu_v, j2d, c2a0, c2a1, c2b1, ga[0], gb[0], ga[1], gb[1]);
+		oU = bU - dt * up.a;
+		oV = bV - dt * up.b;
 	}
 	if (UQ) {
 		// (level activity is wave-uniform, so all lanes of a wavefront agree on nv; the LDS rows were last read by this wavefront)
@@ -1076,7 +1023,8 @@ void tmxk_hypervis(tmx_engine * e, const KParams & p, const double * xsrc, const
 // ---------------------------------------------------------------------------------------------
 // Hyperviscosity pass FUSED with the DSS of the seams inside a patch (round 3 prototype of "remove DSS passes": DESIGN.md
 // section 7).  A workgroup owns a block of up to EB x EB elements of one patch plus the ring of elements around it (where the
-// ring lies inside the patch), evaluates k_hypervis's arithmetic -- statement for statement -- for all of them with the
+// ring lies inside the patch), evaluates k_hypervis's arithmetic -- its pointwise statements from the same functions (tmx_device.h); the two
+// contractions written out here, under `held`: through the shared ones the kernel spills (124 bytes at its cap of 128 registers) -- for all of them with the
 // per-element contractions in LDS, leaves the five results of every node in LDS, and then averages every seam node of its
 // inner elements that is NOT on the patch's boundary from the copies in LDS, in the reference's order (alpha seams before
 // beta seams: 0.5 (x + x'), 0.5 (0.5 (x + x_alpha) + 0.5 (x_beta + x_diag)); inside a patch every copy receives the same
@@ -1142,12 +1090,11 @@ __global__ __launch_bounds__(TMX_HB_T) void k_hypervis_block(KParams p, const Hv
 			ua = xsrc[TMX_SLAB_U(L, kk) * NS + col];
 			ub = xsrc[TMX_SLAB_V(L, kk) * NS + col];
 		}
-		const double cua = c2a0 * ua + c2a1 * ub;
-		const double cub = c2a1 * ua + c2b1 * ub;
+		const ElPair ju = el_flux(j2d, c2a0, c2a1, c2b1, ua, ub);
 		if (t < TMX_HB_N) {
 			s[0][t] = psiT; s[1][t] = psiR; s[2][t] = psiW;
 			s[3][t] = ua;   s[4][t] = ub;
-			s[5][t] = j2d * cua; s[6][t] = j2d * cub;
+			s[5][t] = ju.a; s[6][t] = ju.b;
 		}
 		__syncthreads();
 		double daT = 0, dbT = 0, daR = 0, dbR = 0, daW = 0, dbW = 0, daub = 0, dbua = 0, dajua = 0, dbjub = 0;
@@ -1165,14 +1112,14 @@ __global__ __launch_bounds__(TMX_HB_T) void k_hypervis_block(KParams p, const Hv
 		}
 		daT *= ida; dbT *= idb; daR *= ida; dbR *= idb; daW *= ida; dbW *= idb;
 		daub *= ida; dbua *= idb; dajua *= ida; dbjub *= idb;
-		const double invJ2 = 1.0 / j2d;
-		const double dv = (dajua + dbjub) * invJ2, cl = (daub - dbua) * invJ2;
+		const ElPair fT = el_flux(jn, c2a0, c2a1, c2b1, daT, dbT), fR = el_flux(jn, c2a0, c2a1, c2b1, daR, dbR), fW = el_flux(je, c2a0, c2a1, c2b1, daW, dbW);
+		const ElPair dc = el_div_curl(dajua, dbjub, daub, dbua, 1.0 / j2d);
 		__syncthreads();
 		if (t < TMX_HB_N) {
-			s[0][t] = jn * (c2a0 * daT + c2a1 * dbT); s[1][t] = jn * (c2a1 * daT + c2b1 * dbT);
-			s[2][t] = jn * (c2a0 * daR + c2a1 * dbR); s[3][t] = jn * (c2a1 * daR + c2b1 * dbR);
-			s[4][t] = je * (c2a0 * daW + c2a1 * dbW); s[5][t] = je * (c2a1 * daW + c2b1 * dbW);
-			s[6][t] = dv; s[7][t] = cl;
+			s[0][t] = fT.a; s[1][t] = fT.b;
+			s[2][t] = fR.a; s[3][t] = fR.b;
+			s[4][t] = fW.a; s[5][t] = fW.b;
+			s[6][t] = dc.a; s[7][t] = dc.b;
 		}
 		__syncthreads();
 		double uaT = 0, ubT = 0, uaR = 0, ubR = 0, uaW = 0, ubW = 0, dad = 0, dbd = 0, dac = 0, dbc = 0;
@@ -1190,30 +1137,29 @@ __global__ __launch_bounds__(TMX_HB_T) void k_hypervis_block(KParams p, const Hv
 		}
 		uaT *= ida; ubT *= idb; uaR *= ida; ubR *= idb; uaW *= ida; ubW *= idb;
 		dad *= ida; dbd *= idb; dac *= ida; dbc *= idb;
-		// the five results of this node, exactly k_hypervis's statements; the base value is only known for written nodes,
+		// the five results of this node, by k_hypervis's statements; the base value is only known for written nodes,
 		// so the copies in LDS hold the results with THEIR OWN base: every copy of a seam node has one (duplicated storage)
 		double rW = 0, rT = 0, rR = 0, rU = 0, rV = 0;
 		if (actw) {
 			const size_t o = TMX_SLAB_W(L, kk) * NS + col;
 			const double bs = xbase ? xbase[o] : 0.0;
-			rW = bs - dt * (1.0 / je) * nu_s * (uaW + ubW);
+			rW = el_scalar_update(bs, dt, 1.0 / je, nu_s, uaW, ubW);
 		}
 		if (actn) {
 			const double invJ = 1.0 / jn;
 			size_t o = TMX_SLAB_T(L, kk) * NS + col;
 			double bs = xbase ? xbase[o] : 0.0;
-			rT = bs - dt * invJ * nu_s * (uaT + ubT);
+			rT = el_scalar_update(bs, dt, invJ, nu_s, uaT, ubT);
 			o = TMX_SLAB_R(L, kk) * NS + col;
 			bs = xbase ? xbase[o] : 0.0;
-			rR = bs - dt * invJ * nu_s * (uaR + ubR);
-			const double upa = nu_d * dad - nu_v * j2d * (c2a1 * dac + c2b1 * dbc);
-			const double upb = nu_d * dbd + nu_v * j2d * (c2a0 * dac + c2a1 * dbc);
+			rR = el_scalar_update(bs, dt, invJ, nu_s, uaR, ubR);
+			const ElPair up = el_vector_update(nu_d, nu_v, j2d, c2a0, c2a1, c2b1, dad, dbd, dac, dbc);
 			o = TMX_SLAB_U(L, kk) * NS + col;
 			bs = xbase ? xbase[o] : 0.0;
-			rU = bs - dt * upa;
+			rU = bs - dt * up.a;
 			o = TMX_SLAB_V(L, kk) * NS + col;
 			bs = xbase ? xbase[o] : 0.0;
-			rV = bs - dt * upb;
+			rV = bs - dt * up.b;
 		}
 		__syncthreads();
 		if (t < TMX_HB_N) { s[0][t] = rW; s[1][t] = rT; s[2][t] = rR; s[3][t] = rU; s[4][t] = rV; }
@@ -1269,7 +1215,7 @@ __global__ __launch_bounds__(256) void k_uniform_diffusion(KParams p, const doub
 	const int kk = blockIdx.y * 4 + ty;
 	const bool actw = (kk <= L) && (col < p.ncol);
 	const bool actn = (kk < L) && (col < p.ncol);
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
+	const ElPos ep = el_pos(lane, lane & 48);
 
 	double psiT = 0, psiW = 0, ua = 0, ub = 0, ra = 0, rb = 0;
 	double c2a0 = 0, c2a1 = 0, c2b1 = 0, j2d = 1, jn = 1, je = 1;
@@ -1289,68 +1235,42 @@ __global__ __launch_bounds__(256) void k_uniform_diffusion(KParams p, const doub
 		ua = xsrc[TMX_SLAB_U(L, kk) * NS + col]; ub = xsrc[TMX_SLAB_V(L, kk) * NS + col];
 		ra = xref[TMX_SLAB_U(L, kk) * NS + col]; rb = xref[TMX_SLAB_V(L, kk) * NS + col];
 	}
+	const ElPair ju = el_flux(j2d, c2a0, c2a1, c2b1, ua, ub), jr = el_flux(j2d, c2a0, c2a1, c2b1, ra, rb);
 	s[ty][0][lane] = psiT; s[ty][1][lane] = psiW;
-	s[ty][2][lane] = ua; s[ty][3][lane] = ub; s[ty][4][lane] = j2d * (c2a0 * ua + c2a1 * ub); s[ty][5][lane] = j2d * (c2a1 * ua + c2b1 * ub);
-	s[ty][6][lane] = ra; s[ty][7][lane] = rb; s[ty][8][lane] = j2d * (c2a0 * ra + c2a1 * rb); s[ty][9][lane] = j2d * (c2a1 * ra + c2b1 * rb);
+	s[ty][2][lane] = ua; s[ty][3][lane] = ub; s[ty][4][lane] = ju.a; s[ty][5][lane] = ju.b;
+	s[ty][6][lane] = ra; s[ty][7][lane] = rb; s[ty][8][lane] = jr.a; s[ty][9][lane] = jr.b;
 	__syncthreads();
 
-	double daT = 0, dbT = 0, daW = 0, dbW = 0;
-	double daub = 0, dbua = 0, dajua = 0, dbjub = 0, daubr = 0, dbuar = 0, dajuar = 0, dbjubr = 0;
-#pragma unroll
-	for (int t = 0; t < 4; t++) {
-		const int la = eb + 4 * t + j, lb = eb + 4 * i + t;
-		const double Da = sD[t * 4 + i], Db = sD[t * 4 + j];
-		daT += s[ty][0][la] * Da; dbT += s[ty][0][lb] * Db;
-		daW += s[ty][1][la] * Da; dbW += s[ty][1][lb] * Db;
-		daub += s[ty][3][la] * Da; dbua += s[ty][2][lb] * Db;
-		dajua += s[ty][4][la] * Da; dbjub += s[ty][5][lb] * Db;
-		daubr += s[ty][7][la] * Da; dbuar += s[ty][6][lb] * Db;
-		dajuar += s[ty][8][la] * Da; dbjubr += s[ty][9][lb] * Db;
-	}
+	// gradients of the two scalars, then (d_alpha U_beta, d_beta U_alpha), (d_alpha (J U^alpha), d_beta (J U^beta)) of the state and of the reference
 	const double ida = p.g2d[G2_IDA * NS + col], idb = p.g2d[G2_IDB * NS + col];
-	daT *= ida; dbT *= idb; daW *= ida; dbW *= idb;
-	daub *= ida; dbua *= idb; dajua *= ida; dbjub *= idb;
-	daubr *= ida; dbuar *= idb; dajuar *= ida; dbjubr *= idb;
+	double da[6], db[6];
+	el_deriv(s[ty], sD, ep, { 0, 1, 3, 4, 7, 8 }, { 0, 1, 2, 5, 6, 9 }, ida, idb, da, db);
 	const double invJ2 = 1.0 / j2d;
-	const double dv = (dajua + dbjub) * invJ2, cl = (daub - dbua) * invJ2;
-	const double dvr = (dajuar + dbjubr) * invJ2, clr = (daubr - dbuar) * invJ2;
+	const ElPair fT = el_flux(jn, c2a0, c2a1, c2b1, da[0], db[0]), fW = el_flux(je, c2a0, c2a1, c2b1, da[1], db[1]);
+	const ElPair dc = el_div_curl(da[3], db[3], da[2], db[2], invJ2), dcr = el_div_curl(da[5], db[5], da[4], db[4], invJ2);
 	__syncthreads();
-	s[ty][0][lane] = jn * (c2a0 * daT + c2a1 * dbT); s[ty][1][lane] = jn * (c2a1 * daT + c2b1 * dbT);
-	s[ty][2][lane] = je * (c2a0 * daW + c2a1 * dbW); s[ty][3][lane] = je * (c2a1 * daW + c2b1 * dbW);
-	s[ty][4][lane] = dv; s[ty][5][lane] = cl; s[ty][6][lane] = dvr; s[ty][7][lane] = clr;
+	s[ty][0][lane] = fT.a; s[ty][1][lane] = fT.b;
+	s[ty][2][lane] = fW.a; s[ty][3][lane] = fW.b;
+	s[ty][4][lane] = dc.a; s[ty][5][lane] = dc.b; s[ty][6][lane] = dcr.a; s[ty][7][lane] = dcr.b;
 	__syncthreads();
 	if (!actw) return;
 
-	double uaT = 0, ubT = 0, uaW = 0, ubW = 0, dad = 0, dbd = 0, dac = 0, dbc = 0, dadr = 0, dbdr = 0, dacr = 0, dbcr = 0;
-#pragma unroll
-	for (int t = 0; t < 4; t++) {
-		const int la = eb + 4 * t + j, lb = eb + 4 * i + t;
-		const double Sa = sS[i * 4 + t], Sb = sS[j * 4 + t];
-		uaT += s[ty][0][la] * Sa; ubT += s[ty][1][lb] * Sb;
-		uaW += s[ty][2][la] * Sa; ubW += s[ty][3][lb] * Sb;
-		dad -= Sa * s[ty][4][la]; dbd -= Sb * s[ty][4][lb];
-		dac -= Sa * s[ty][5][la]; dbc -= Sb * s[ty][5][lb];
-		dadr -= Sa * s[ty][6][la]; dbdr -= Sb * s[ty][6][lb];
-		dacr -= Sa * s[ty][7][la]; dbcr -= Sb * s[ty][7][lb];
-	}
-	uaT *= ida; ubT *= idb; uaW *= ida; ubW *= idb;
-	dad *= ida; dbd *= idb; dac *= ida; dbc *= idb; dadr *= ida; dbdr *= idb; dacr *= ida; dbcr *= idb;
+	double wa[2], wb[2], ga[4], gb[4];
+	el_stiff(s[ty], sS, ep, { 0, 2 }, { 1, 3 }, { 4, 5, 6, 7 }, ida, idb, wa, wb, ga, gb);
 	{
 		const size_t o = TMX_SLAB_W(L, kk) * NS + col;
-		xout[o] = oW - dt * (1.0 / je) * kv * (uaW + ubW);
+		xout[o] = el_scalar_update(oW, dt, 1.0 / je, kv, wa[1], wb[1]);
 	}
 	if (actn) {
 		size_t o = TMX_SLAB_T(L, kk) * NS + col;
-		xout[o] = oT - dt * (1.0 / jn) * ks * (uaT + ubT);
+		xout[o] = el_scalar_update(oT, dt, 1.0 / jn, ks, wa[0], wb[0]);
 		const double nkv = -kv;
-		const double upa = nkv * dad - nkv * j2d * (c2a1 * dac + c2b1 * dbc);
-		const double upb = nkv * dbd + nkv * j2d * (c2a0 * dac + c2a1 * dbc);
-		const double upar = kv * dadr - kv * j2d * (c2a1 * dacr + c2b1 * dbcr);
-		const double upbr = kv * dbdr + kv * j2d * (c2a0 * dacr + c2a1 * dbcr);
+		const ElPair up = el_vector_update(nkv, nkv, j2d, c2a0, c2a1, c2b1, ga[0], gb[0], ga[1], gb[1]);
+		const ElPair upr = el_vector_update(kv, kv, j2d, c2a0, c2a1, c2b1, ga[2], gb[2], ga[3], gb[3]);
 		o = TMX_SLAB_U(L, kk) * NS + col;
-		double v = oU; v -= dt * upa; v -= dt * upar; xout[o] = v;
+		double v = oU; v -= dt * up.a; v -= dt * upr.a; xout[o] = v;
 		o = TMX_SLAB_V(L, kk) * NS + col;
-		v = oV; v -= dt * upb; v -= dt * upbr; xout[o] = v;
+		v = oV; v -= dt * up.b; v -= dt * upr.b; xout[o] = v;
 	}
 }
 

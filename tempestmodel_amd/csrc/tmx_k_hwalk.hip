@@ -105,37 +105,21 @@ __global__ __launch_bounds__(64) void k_ref_diffusion_terms(KParams p, const dou
 	const int colr = blockIdx.x * 64 + lane;
 	const bool here = colr < p.ncol;
 	const int col = here ? colr : p.ncol - 1;
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
+	const ElPos ep = el_pos(lane, lane & 48);
 	const double c2a0 = p.g2d[G2_C2A0 * NS + col], c2a1 = p.g2d[G2_C2A1 * NS + col], c2b1 = p.g2d[G2_C2B1 * NS + col];
 	const double j2d = p.g2d[G2_J2D * NS + col], ida = p.g2d[G2_IDA * NS + col], idb = p.g2d[G2_IDB * NS + col];
 	const double ra = xref[TMX_SLAB_U(L, k) * NS + col], rb = xref[TMX_SLAB_V(L, k) * NS + col];
-	s[0][lane] = ra; s[1][lane] = rb; s[2][lane] = j2d * (c2a0 * ra + c2a1 * rb); s[3][lane] = j2d * (c2a1 * ra + c2b1 * rb);
+	const ElPair jr = el_flux(j2d, c2a0, c2a1, c2b1, ra, rb);
+	s[0][lane] = ra; s[1][lane] = rb; s[2][lane] = jr.a; s[3][lane] = jr.b;
 	__syncthreads();
-	double daubr = 0, dbuar = 0, dajuar = 0, dbjubr = 0;
-#pragma unroll
-	for (int t = 0; t < 4; t++) {
-		const int la = eb + 4 * t + j, lb = eb + 4 * i + t;
-		const double Da = sD[t * 4 + i], Db = sD[t * 4 + j];
-		daubr += s[1][la] * Da; dbuar += s[0][lb] * Db;
-		dajuar += s[2][la] * Da; dbjubr += s[3][lb] * Db;
-	}
-	daubr *= ida; dbuar *= idb; dajuar *= ida; dbjubr *= idb;
-	const double invJ2 = 1.0 / j2d;
-	const double dvr = (dajuar + dbjubr) * invJ2, clr = (daubr - dbuar) * invJ2;
+	double da[2], db[2], ga[2], gb[2];
+	el_deriv(s, sD, ep, { 1, 2 }, { 0, 3 }, ida, idb, da, db);
+	const ElPair dcr = el_div_curl(da[1], db[1], da[0], db[0], 1.0 / j2d);
 	__syncthreads();
-	s[0][lane] = dvr; s[1][lane] = clr;
+	s[0][lane] = dcr.a; s[1][lane] = dcr.b;
 	__syncthreads();
-	double dadr = 0, dbdr = 0, dacr = 0, dbcr = 0;
-#pragma unroll
-	for (int t = 0; t < 4; t++) {
-		const int la = eb + 4 * t + j, lb = eb + 4 * i + t;
-		const double Sa = sS[i * 4 + t], Sb = sS[j * 4 + t];
-		dadr -= Sa * s[0][la]; dbdr -= Sb * s[0][lb];
-		dacr -= Sa * s[1][la]; dbcr -= Sb * s[1][lb];
-	}
-	dadr *= ida; dbdr *= idb; dacr *= ida; dbcr *= idb;
-	const double upar = kv * dadr - kv * j2d * (c2a1 * dacr + c2b1 * dbcr);
-	const double upbr = kv * dbdr + kv * j2d * (c2a0 * dacr + c2a1 * dbcr);
+	el_wgrad(s, sS, ep, { 0, 1 }, ida, idb, ga, gb);
+	const ElPair upr = el_vector_update(kv, kv, j2d, c2a0, c2a1, c2b1, ga[0], gb[0], ga[1], gb[1]);
 	// DiffDiffNodeToNode of the reference's U, V (the accumulation of k_v_explicit_slide / v_explicit_point: in-range levels, offsets ascending)
 	double ddr[2] = { 0.0, 0.0 };
 #pragma unroll
@@ -147,7 +131,7 @@ __global__ __launch_bounds__(64) void k_ref_diffusion_terms(KParams p, const dou
 		ddr[1] += c * xref[TMX_SLAB_V(L, l) * NS + col];
 	}
 	if (!here) return;
-	xrefd[TMX_REFD_HU(L, k) * NS + col] = upar; xrefd[TMX_REFD_HV(L, k) * NS + col] = upbr;
+	xrefd[TMX_REFD_HU(L, k) * NS + col] = upr.a; xrefd[TMX_REFD_HV(L, k) * NS + col] = upr.b;
 	xrefd[TMX_REFD_DU(L, k) * NS + col] = ddr[0]; xrefd[TMX_REFD_DV(L, k) * NS + col] = ddr[1];
 }
 template <int NT, bool PM, bool DM, bool BLK = false, bool EM = false, bool UQ = true, bool FV = true, bool UD = false>
@@ -432,6 +416,8 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 		if constexpr (UD) {
 			// horizontal uniform diffusion of rho*theta, W (relative to the reference state) and of U, V (divergence / curl form, state and reference
 			// apart), k_uniform_diffusion's statements on this level's values; the stage combination's terms are reduced by now (their registers are free)
+			// (written out, not taken from tmx_device.h as k_uniform_diffusion's are: the split second pass with the shared contractions moved the register
+			// count of 10 of the 36 instantiations and the scratch of one; profiles/viscosity_operators_statement_list.md)
 			wave_sync();
 			const double psiT = t0 - rfT, psiW = w0 - rfW;
 			s[0][lp] = psiT; s[1][lp] = psiW;
@@ -726,7 +712,8 @@ void tmxk_h_walk(tmx_engine * e, const KParams & p, const StageIO & st) {
 
 // ---------------------------------------------------------------------------------------------
 // The hyperviscosity pass of the node-unique layout as a walk: k_hypervis<false, UQ, HB> (tmx_k_horizontal.hip; ApplyScalarHyperdiffusion /
-// ApplyVectorHyperdiffusion, HorizontalDynamicsFEM.cpp:1867-2414), statement for statement, with a wavefront walking a segment of the L + 1
+// ApplyVectorHyperdiffusion, HorizontalDynamicsFEM.cpp:1867-2414), statement for statement (written out, not taken from tmx_device.h: with the shared
+// operators the pass without a base instance ran 1.5 % longer per launch, profiles/viscosity_operators_statement_list.md), with a wavefront walking a segment of the L + 1
 // levels (the last one holds W of the lid alone): the nine per-column geometry values, the seam tables and the viscosity coefficients once
 // per segment instead of once per level (11 of the level-parallel kernel's 21 loads per thread and level), the next level's five fields and
 // five base values in flight during this level's two rounds of contractions.  No coupling between levels: any split into segments will do.

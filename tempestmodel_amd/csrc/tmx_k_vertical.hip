@@ -143,6 +143,21 @@ void tmxk_v_explicit(tmx_engine * e, const KParams & p, const double * xin, doub
 		hipLaunchKernelGGL(k_v_explicit<false>, grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)nullptr, 0.0, nt_, xm);
 }
 
+// VerticalDynamicsFEM::UpdateColumnTracers (VerticalDynamicsFEM.cpp:3783-4282), implicit mode, vertical order 1:
+// one lane per unique column.  The tridiagonal matrix (kl = ku = 1) is kept in LAPACK band storage
+// AB(i, j) = sm[(j * 4 + 2 + i - j)] and factorised / solved with the dgbtf2 / dgbtrs loops (first-maximum
+// pivoting, column-oriented back substitution) -- the restatement oracle/tmx_oracle.c:orc_dgbsv pins against
+// LAPACK -- once per tracer on a fresh copy, which is what dgbtrf + dgbtrs per tracer compute.
+// xin: initial instance (U, V, tracer densities), w0: W of the initial column [L+1][NS] (a saved copy when the step
+// runs in place and the state kernel has already overwritten it), xup: update instance (updated W; receives the tracers),
+// xbase: instance holding the tracer values the update is subtracted from (the update instance itself in the
+// reference; the initial instance when the preceding CopyData was fused away).
+// expl (fully explicit vertical mode, :3910-3912, :4047-4063, :4117-4141, :4166-4170, :4193): every stored column is
+// advanced on its own (ucol == udep == nullptr; the update instance has not been through the DSS yet), the matrix is
+// the diagonal 1/dt (dgbtrs then is one division per level), xi_dot comes from the initial W for both uses, there
+// is no velocity correction, and with ks != 0 the mass flux carries the uniform diffusion of q / rho - (q / rho)_ref.
+// LW = columns per workgroup (the lane stride of the LDS arrays): 64, or 32 when (8L + 2) x 512 bytes exceed the 160 KB of a
+// CU (L >= 40, e.g. the 40 levels of the DCMIP2016 supercell) -- half-filled wavefronts, twice the workgroups.
 template <int LW>
 __global__ __launch_bounds__(64) void k_vi_tracers(KParams p, int nt, const double * __restrict__ xin, const double * __restrict__ w0,
 	const double * xbase, double * xup, double dt, int nunique, const int * __restrict__ ucol, const int * __restrict__ udep, int * __restrict__ flag,

@@ -149,6 +149,35 @@ def test_hyperviscosity_fused_with_the_in_patch_dss_is_bit_identical(ne, npatch,
             assert np.array_equal(ae[3, 1:-1, 1:-1], be[3, 1:-1, 1:-1])
 
 
+def test_hyperviscosity_fused_with_the_in_patch_dss_vs_oracle(monkeypatch):
+    """k_hypervis_block against the C ORACLE: the test above compares it with k_hypervis, and both take the pointwise statements of the
+    viscosity operators from the same functions (tmx_device.h), so a wrong statement there moves both alike.  The smallest grid on which
+    the kernel can go wrong -- ne3 on 6 patches: one clipped block of 3 x 3 elements per patch, no ring, every seam inside a patch
+    averaged in the kernel, L = 4 (the interface level L with W alone in a level group of its own) -- two ARS343 steps, == 0.0;
+    tmx_info(TMX_INFO_HYPERVIS_KERNEL) stays -1: neither k_hypervis nor k_hv_walk, which record themselves there, ran a pass."""
+    from tempestmodel_amd.engine import Engine
+    from oracle_lib import Oracle
+    g, states = gu.make_grid(3, 4, 6)
+    o = Oracle(g); o.set_state(0, states)
+    for _ in range(2):
+        assert o.step_ars343(100.0) == 0
+    want = o.get_state(0)
+    assert all(np.isfinite(n).all() and np.isfinite(e_).all() for n, e_ in want)
+    monkeypatch.setenv("TMX_HVIS_BLOCK", "1")
+    e = Engine(g, flavour="experiments")      # (an archived kernel: experiments flavour of the library)
+    try:
+        e.upload_state(0, states)
+        for _ in range(2):
+            e.step_ars343(100.0)
+        e.sync()
+        assert e.info(23) == -1, e.info(23)
+        errs = gu.prognostic_errors(e.download_state(0), want)
+        print("k_hypervis_block, two ARS343 steps at ne3 L4 against the oracle:", errs)
+        assert max(errs) == 0.0, errs
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("ne,npatch,shape,blocks", [(5, 6, 4, -1), (7, 6, 4, -1), (6, 24, 4, -1), (5, 6, 3, 1), (6, 24, 0, 1), (5, 6, 4, 0)])
 @pytest.mark.parametrize("scheme", ["ars343", "strang", "ark232"])
 def test_block_kernels_and_block_thread_orders_are_bit_identical(scheme, ne, npatch, shape, blocks):
