@@ -453,6 +453,7 @@ void tmxk_pack_p2p(tmx_engine * e, const KParams & p, const double * x, int buf)
 void tmxk_p2p_signal_wait(tmx_engine * e, hipStream_t s, int buf, unsigned long long seq);
 void tmxk_rayleigh(tmx_engine * e, const KParams & p, double * x, double dt, const double * xs = nullptr, size_t NSS = 0, const int * ucd = nullptr);
 void tmxk_held_suarez(tmx_engine * e, const KParams & p, double * x, const double * surf, double dt, const double * xs = nullptr, size_t NSS = 0, const int * ucd = nullptr);
+#define TMX_KES_NW 8      // k_kessler's column work arrays [TMX_KES_NW][L][NS] (d_kes, allocated at first use)
 void tmxk_kessler(tmx_engine * e, const KParams & p, double * x, double dt);
 // DCMIP2016_PHYSICS per column (tmx_k_physics.hip).  Column inputs [TMX_DC_NCOEF][NS]: RLL-from-ABP coefficients (lon <- a, lon <- b,
 // lat <- a, lat <- b, cos(lat) factor of lon), ABP-from-RLL (cos(lat) divisor of lon, a <- lon, a <- lat, b <- lon, b <- lat), Tsurf of test 1

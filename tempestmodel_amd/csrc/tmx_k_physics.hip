@@ -78,8 +78,12 @@ void tmxk_held_suarez(tmx_engine * e, const KParams & p, double * x, const doubl
 // Column physics: KesslerPhysics::Perform (test/dcmip2016/KesslerPhysics.cpp:83-285) around SUBROUTINE KESSLER
 // (test/dcmip2016/interface/kessler.f90:64-185), Lorenz staggering / FORMULATION_RHOTHETA_PI; tracers 0,1,2 = RhoQv,
 // RhoQc, RhoQr.  One lane per stored column (the reference visits every interior node of a patch, duplicated element-edge
-// nodes included), three sweeps over the levels; the column's work arrays live in an HBM scratch [8][L][NS] (coalesced
-// across lanes) instead of the Fortran automatic arrays.  The arithmetic is the subroutine's as the reference's build
+// nodes included), three sweeps over the levels; the column's work arrays live in an HBM scratch [KES_NF][L][NS] (coalesced
+// across lanes) instead of the Fortran automatic arrays.  The subroutine is dealt out three ways: k_kessler holds it inline,
+// k_kessler_tile (level-parallel) and the PREC == 0 branch of k_dcmip (one lane per column inside its own work arrays) call
+// the level functions below; k_dcmip repeats k_kessler's CFL loop and rain-loop frame on purpose -- one shared frame over a
+// record of column pointers ran k_kessler 4 % (bodies inlined) or 12 % (through the level functions) and k_dcmip 3 % longer
+// at L = 60 (profiles/kessler_statement_list.md) -- and shares its sedimentation term (kes_sed).  The arithmetic is the subroutine's as the reference's build
 // compiles it (mk/defs.make:35: no default-real-8 flag): r, rhalf, velqr, sed, pc are SINGLE precision, real literals
 // without d0 are single precision values promoted to double, AMAX1 / AMIN1 convert their arguments to single precision
 // (oracle/tmx_oracle.c:orc_kessler_column is the same restatement, bit for bit against the compiled Fortran).
@@ -94,8 +98,14 @@ __device__ __forceinline__ double kes_amin1(double a, double b, double c) {
 __device__ __forceinline__ float kes_velqr(double qr, float r, float rhalf) {
 	return (float)(36.34 * tmx_ref_pow(qr * (double)r, (double)0.1364f) * (double)rhalf);      // kessler.f90:113, :170
 }
+// kessler.f90:139-142 for the two column kernels (k_kessler, k_dcmip); z_a - z_b: z(k+1) - z(k), top level: z(k) - z(k-1)
+__device__ __forceinline__ float kes_sed(double dt0, float r_k, double qr_k, float vel_k, float r_n, double qr_n, float vel_n, double z_a, double z_b, bool top) {
+	if (top) return (float)(-dt0 * qr_k * (double)vel_k / ((double)0.5f * (z_a - z_b)));       // :142
+	return (float)(dt0 * ((double)r_n * qr_n * (double)vel_n - (double)r_k * qr_k * (double)vel_k) / ((double)r_k * (z_a - z_b)));     // :139-141
+}
 
 enum { KES_TH = 0, KES_QV, KES_QC, KES_QR, KES_PK, KES_RHOD, KES_PC, KES_VEL, KES_NF };
+static_assert(KES_NF == TMX_KES_NW, "work array count");
 
 __global__ __launch_bounds__(256) void k_kessler(KParams p, double * __restrict__ x, const double * __restrict__ zlev,
 	double * __restrict__ w, double * __restrict__ prect, double dt, double gamma, double pscal)
@@ -149,9 +159,9 @@ __global__ __launch_bounds__(256) void k_kessler(KParams p, double * __restrict_
 			if (k < L - 1) {
 				qr_n = WK(KES_QR, k + 1); rhod_n = WK(KES_RHOD, k + 1); z_n = zlev[(size_t)(k + 1) * NS + col];
 				vel_n = (float)WK(KES_VEL, k + 1); r_n = (float)(0.001 * rhod_n);
-				sed = (float)(dt0 * ((double)r_n * qr_n * (double)vel_n - (double)r_k * qr_k * (double)vel_k) / ((double)r_k * (z_n - z_k)));     // :139-141
+				sed = kes_sed(dt0, r_k, qr_k, vel_k, r_n, qr_n, vel_n, z_n, z_k, false);
 			} else {
-				sed = (float)(-dt0 * qr_k * (double)vel_k / ((double)0.5f * (z_k - z_km)));       // :142
+				sed = kes_sed(dt0, r_k, qr_k, vel_k, r_n, qr_n, vel_n, z_k, z_km, true);
 			}
 			double th = WK(KES_TH, k), qv = WK(KES_QV, k), qc = WK(KES_QC, k), qr = qr_k;
 			const double pk = WK(KES_PK, k), pc = WK(KES_PC, k);
@@ -207,9 +217,12 @@ __global__ __launch_bounds__(256) void k_kessler(KParams p, double * __restrict_
 // results are bit-identical.  No HBM work arrays (ne30 L40: 0.18 GB per call instead of 1.02 GB) and 6 480 wavefronts instead of
 // 810 (one lane per column leaves most SIMDs without a wavefront): 397 -> 275 us per call there.  What is left is the fp64
 // arithmetic of nine exp / log / pow evaluations per level (about 140 us at the chip's fp64 rate).
-// one level of one sub-cycle (kessler.f90:147-172) and the inputs of one level (KesslerPhysics.cpp:147-220, kessler.f90:107-115)
-// as functions that are NOT inlined: the level-parallel kernel below calls them for the KES_NO levels a thread owns, and
-// inlined five times over the compiler interleaves the copies and runs out of registers (256 + spills)
+//
+// The level functions: one level of one sub-cycle (kessler.f90:147-172), the inputs of one level (KesslerPhysics.cpp:147-220)
+// and its pc / velqr (kessler.f90:107-115), NOT inlined: the level-parallel kernel below calls them for the KES_NO levels a
+// thread owns, and inlined five times over the compiler interleaves the copies and runs out of registers (256 + spills);
+// k_dcmip calls kes_level_pc_vel and kes_sweep_level once per level.  They restate k_kessler's statements: a correction to
+// one is a correction to the other
 struct KesLevel { double th, qv, qc, qr; float vel; };
 __device__ __attribute__((noinline)) KesLevel kes_sweep_level(KesLevel s, double pk_, double pc_, double rhod_k, double rhod0, float sed, double dt0, int new_vel)
 {
@@ -466,7 +479,7 @@ __global__ __launch_bounds__(64) void k_dcmip(KParams p, double * __restrict__ x
 			}
 		}
 	} else {
-		// ---- :260-292 Kessler: exner and theta, SUBROUTINE KESSLER (kessler.f90:64-185, the level functions of k_kessler_tile), back ----
+		// ---- :260-292 Kessler: exner and theta, SUBROUTINE KESSLER (kessler.f90:64-185: the level functions of k_kessler_tile in k_kessler's CFL loop and rain-loop frame), back ----
 		const double rhod0 = DW(DW_RHOD, 0);
 		double dt_max = dt, z_prev = 0.0; float vel_prev = 0.0f;
 		for (int k = 0; k < L; k++) {
@@ -493,9 +506,9 @@ __global__ __launch_bounds__(64) void k_dcmip(KParams p, double * __restrict__ x
 				if (k < L - 1) {
 					qr_n = DW(DW_QR, k + 1); rhod_n = DW(DW_RHOD, k + 1); z_n = ZL(k + 1);
 					vel_n = (float)DW(DW_VEL, k + 1); r_n = (float)(0.001 * rhod_n);
-					sed = (float)(dt0 * ((double)r_n * qr_n * (double)vel_n - (double)r_k * qr_k * (double)vel_k) / ((double)r_k * (z_n - z_k)));
+					sed = kes_sed(dt0, r_k, qr_k, vel_k, r_n, qr_n, vel_n, z_n, z_k, false);
 				} else {
-					sed = (float)(-dt0 * qr_k * (double)vel_k / ((double)0.5f * (z_k - z_km)));
+					sed = kes_sed(dt0, r_k, qr_k, vel_k, r_n, qr_n, vel_n, z_k, z_km, true);
 				}
 				KesLevel lv; lv.th = DW(DW_TH, k); lv.qv = DW(DW_QV, k); lv.qc = DW(DW_QC, k); lv.qr = qr_k; lv.vel = vel_k;
 				lv = kes_sweep_level(lv, DW(DW_PK, k), DW(DW_PC, k), rhod_k, rhod0, sed, dt0, nt != rainsplit);

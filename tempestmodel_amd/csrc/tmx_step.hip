@@ -902,8 +902,8 @@ extern "C" int tmx_physics_kessler(tmx_engine * e, int instance, double dt) {
 	const size_t NS = e->NS; const int L = e->L;
 	if ((r = column_physics_levels(e))) return r;
 	if (!e->d_kes) {
-		HIPCHK(hipMalloc((void **)&e->d_kes, (size_t)8 * L * NS * sizeof(double)));
-		e->hbm_bytes += (size_t)8 * L * NS * sizeof(double);
+		HIPCHK(hipMalloc((void **)&e->d_kes, (size_t)TMX_KES_NW * L * NS * sizeof(double)));
+		e->hbm_bytes += (size_t)TMX_KES_NW * L * NS * sizeof(double);
 	}
 	ProfScope ps(e, TMX_K_LINCOMB);
 	tmxk_kessler(e, make_params(e), inst(e, instance), dt);
