@@ -948,6 +948,11 @@ static void filter_negative_tracers_v(const orc_grid * g, orc_state * s, int iup
 	}
 }
 
+/* both filters on their own, for the tests that hold the device's fused and stand-alone filters to them */
+void orc_filter_negative_tracers(const orc_grid * g, orc_state * s, int ix, int vertical) {
+	if (vertical) filter_negative_tracers_v(g, s, ix); else filter_negative_tracers_h(g, s, ix);
+}
+
 int orc_v_step_implicit(const orc_grid * g, orc_state * s, int iinit, int iupd, double dt) {
 	if (g->fully_explicit) return 0;      /* VerticalDynamicsFEM::StepImplicit, :1239-1242 */
 	if (g->shallow_water) return 0;    /* VerticalDynamicsStub */

@@ -129,6 +129,10 @@ void orc_h_step_explicit(const orc_grid * g, orc_state * s, int iinit, int iupd,
 void orc_v_step_explicit(const orc_grid * g, orc_state * s, int iinit, int iupd, double dt);
 int  orc_v_step_implicit(const orc_grid * g, orc_state * s, int iinit, int iupd, double dt);
 void orc_apply_dss(const orc_grid * g, orc_state * s, int ix);
+/* FilterNegativeTracers in place on instance ix: vertical == 0 HorizontalDynamicsFEM's (per element, level and tracer: the tail of
+ * orc_h_step_explicit and of orc_h_step_after_subcycle), != 0 VerticalDynamicsFEM's (per column and tracer: the tail of
+ * orc_v_step_implicit and of Strang's carry-over step).  Nothing without tracers. */
+void orc_filter_negative_tracers(const orc_grid * g, orc_state * s, int ix, int vertical);
 void orc_h_step_after_subcycle(const orc_grid * g, orc_state * s, int iinit, int iupd, int iwork, double dt);
 int  orc_step_ars343(const orc_grid * g, orc_state * s, double dt);
 void orc_v_step_implicit_terms_explicitly(const orc_grid * g, orc_state * s, int iinit, int iupd, double dt);

@@ -231,6 +231,14 @@ class Oracle:
     def apply_dss(self, ix):
         lib().orc_apply_dss(C.byref(self.cgrid), C.byref(self.cstate), ix)
 
+    def filter_negative_tracers_h(self, ix):
+        """HorizontalDynamicsFEM::FilterNegativeTracers in place on instance ix (per element, level and tracer)."""
+        lib().orc_filter_negative_tracers(C.byref(self.cgrid), C.byref(self.cstate), ix, 0)
+
+    def filter_negative_tracers_v(self, ix):
+        """VerticalDynamicsFEM::FilterNegativeTracers in place on instance ix (per column and tracer)."""
+        lib().orc_filter_negative_tracers(C.byref(self.cgrid), C.byref(self.cstate), ix, 1)
+
     def h_step_after_subcycle(self, iinit, iupd, iwork, dt):
         lib().orc_h_step_after_subcycle(C.byref(self.cgrid), C.byref(self.cstate), iinit, iupd, iwork, C.c_double(dt))
 
