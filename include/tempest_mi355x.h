@@ -476,7 +476,13 @@ long long tmx_info(tmx_engine * e, int what);
  *                        fourth stage reads 3 instances instead of 7); 0: every stage reads all its terms.  Same bits.
  *   "lu_fma"            band LU of the column solves (LAPACK::DGBSV, src/base/LinearAlgebra.cpp:156-202): 1 (default) = updates a - l u fused
  *                        (a reference linked to OpenBLAS, or to MKL on its FMA code paths), 0 = multiply and subtract rounded separately
- *                        (a BLAS without fused multiply-adds).  tmx_lu_flavour_from_dgbsv (below) asks the caller's own LAPACK.
+ *                        (a BLAS without fused multiply-adds).  tmx_lu_flavour_from_dgbsv (below) asks the caller's own LAPACK.  The kernels that
+ *                        hold a band LU -- the column solve of V.StepImplicit and the implicit column update of the tracers -- are compiled in
+ *                        both roundings; every other kernel is compiled once and does not depend on the option.
+ *   "vt_rows"           implicit column update of the tracers (UpdateColumnTracers): 1 (default) = several row lanes per column, 0 = the same
+ *                        kernel with one row lane per column, i.e. the serial order (cross-check of the row-lane decomposition; same bits).
+ *   "vt_column"         fully explicit vertical mode: 1 = the tracer column update by a one-lane-per-column kernel of its own (cross-check of
+ *                        the column walks and level-parallel kernels; same bits).
  * Archived experiments and cross-check kernels -- "unique_blocks", "unique_tile_shape" = 3, 4, "hvis_pull", "hvis_block", "vi_split_kernels", "vi_pair" = 0,
  * "vi_carry", "vi_sparse", "vi_split_back", "vi_back_sub", "vx_fused", "vt_explicit_v1", "debug_skip_exchange" -- are compiled into the
  * experiments flavour of the library only (libtempest_mi355x_exp.so, `make -C tempestmodel_amd/csrc exp`; tmx_info(TMX_INFO_EXPERIMENTS_BUILD)):

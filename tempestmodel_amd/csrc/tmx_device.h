@@ -20,8 +20,9 @@
 // (-ffp-contract=off), as the reference's own C++ is compiled without FMA contraction.
 // The band LU's updates a - l * u: fused multiply-adds, as OpenBLAS's and MKL's kernels evaluate them on x86-64-v3 hosts
 // (DESIGN.md section 2).  A reference linked to a BLAS WITHOUT fused multiply-adds (a plain netlib build, MKL on some AMD
-// hosts) is reproduced by the library's second build flavour, `make nofma` -> libtempest_mi355x_nofma.so (-DTMX_LU_NOFMA,
-// selected by TMX_LU_FMA=0 in engine.py / by linking it): multiply and subtract, rounded separately (-ffp-contract=off).
+// hosts) is reproduced by multiply and subtract, rounded separately (-ffp-contract=off): the translation units whose kernels use
+// LU_UPD (the Makefile's SRC_LU: tmx_k_column.hip, tmx_k_tracer_solve.hip) are compiled a second time with -DTMX_LU_NOFMA into
+// the same library, and the engine's option "lu_fma" = 0 (TMX_LU_FMA=0) selects that pass at run time (tmx_lu_select.hip).
 #ifdef TMX_LU_NOFMA
 #define LU_UPD(a, l, u) ((a) - (l) * (u))
 #else

@@ -13,11 +13,15 @@
 // order of the reference (which is built without FMA contraction).
 //
 // Reference behaviour restated (file:line under the reference tree) is cited per kernel.
-#include "tmx_device.h"
+#include "tmx_device_column.h"
 
-// Both flavours of the band LU live in ONE library: this translation unit is compiled twice -- as it stands (LU updates fused, what OpenBLAS
-// and MKL's FMA code paths compute) and with -DTMX_LU_NOFMA (multiply and subtract rounded separately, a BLAS without fused multiply-adds:
-// tmx_device.h, LU_UPD) -- into a namespace each; tmx_lu_select.hip dispatches by the engine's option "lu_fma" (tmx_set_option, any time).
+// Both flavours of the band LU live in ONE library.  The rule: a translation unit whose kernels use LU_UPD (tmx_device.h) is compiled twice
+// -- as it stands (LU updates fused, what OpenBLAS and MKL's FMA code paths compute) and with -DTMX_LU_NOFMA (multiply and subtract rounded
+// separately, a BLAS without fused multiply-adds) -- into a namespace each; tmx_lu_select.hip dispatches by the engine's option "lu_fma"
+// (tmx_set_option, any time).  This unit holds the column solve and nothing else: k_vi_pair, k_vi_group and, in the experiments flavour,
+// k_vi_fused, k_vi_back and the split pair k_vi_assemble / k_vi_solve (k_vi_assemble holds no LU; it stays beside k_vi_solve, whose
+// input it writes, in the one TMX_EXP block).  The block-row assembly they share with StepImplicitTermsExplicitly is tmx_device_column.h;
+// that operator itself (k_vi_terms_explicit, no LU) is in tmx_k_vertical.hip, compiled once.
 #ifdef TMX_LU_NOFMA
 namespace lu_nofma {
 #else
@@ -49,8 +53,7 @@ __global__ __launch_bounds__(256) void k_vi_assemble(KParams p, const double * _
 #pragma unroll
 	for (int d = 0; d < TMX_BW; d++) { rowP[d] = 0.0; rowW[d] = 0.0; rowR[d] = 0.0; }
 	double fP = 0.0, fW = 0.0, fR = 0.0;
-	// band offset of column (c', k') seen from row (c, k): d = 3(k'-k) + (c'-c) + 4
-#define DOFF(cr, cc, dk) (3 * (dk) + ((cc) - (cr)) + 4)
+	// (band offset of column (c', k') seen from row (c, k): DOFF, tmx_device_column.h)
 
 	auto ldn = [&](int slabbase, int l) -> double {      // node slab, clamped level
 		const int lc = l < 0 ? 0 : (l > L - 1 ? L - 1 : l);
@@ -248,7 +251,6 @@ __global__ __launch_bounds__(256) void k_vi_assemble(KParams p, const double * _
 	RHS[(size_t)(r0 + 0) * NUS + u] = fP;
 	RHS[(size_t)(r0 + 1) * NUS + u] = fW;
 	RHS[(size_t)(r0 + 2) * NUS + u] = fR;
-#undef DOFF
 }
 
 void tmxk_vi_assemble(tmx_engine * e, const KParams & p, const double * xin, double dt) {
@@ -386,245 +388,7 @@ void tmxk_vi_solve(tmx_engine * e, const KParams & p, const double * xin, double
 // the three levels a block row touches lives in a sliding register window; the loads of the next
 // level are issued one block (three pivot steps) ahead of their first use.
 // Arithmetic is statement-for-statement that of the split kernels: results are bit-identical.
-
-struct NodeLev { double un, vn, pn, rn, ca2, cb2, cx2; };
-struct EdgeLev { double we, ce0, ce1, ce2; };
-
-// Loads are unconditional with the level clamped into range: a fixed number of loads per block row keeps the
-// compiler's vmcnt bookkeeping exact, so a wait for the previous block row's prefetch does not also wait for
-// the loads just issued.  Out-of-range levels (-1 below block row 0, L and L+1 past the top) therefore carry
-// the values of the nearest level; compute_block only touches them under its k >= 1 / k + 1 <= L - 1 guards or
-// with zero operator coefficients, so results do not depend on them (checked bitwise against the split kernels).
-template <int MM = 0>
-__device__ __forceinline__ NodeLev load_node(const KParams & p, const MetCol & mc, const double * xin, int l, int col, const double * etal = nullptr) {
-	NodeLev n;
-	const int L = p.L;
-	const int lc = l < 0 ? 0 : (l >= L ? L - 1 : l);
-	const size_t NS = (size_t)p.NS;
-	n.un = xin[TMX_SLAB_U(L, lc) * NS + col]; n.vn = xin[TMX_SLAB_V(L, lc) * NS + col];
-	n.pn = xin[TMX_SLAB_T(L, lc) * NS + col]; n.rn = xin[TMX_SLAB_R(L, lc) * NS + col];
-	metric_node3<MM>(p, mc, lc, col, n.ca2, n.cb2, n.cx2, etal);
-	return n;
-}
-template <int MM = 0>
-__device__ __forceinline__ EdgeLev load_edge(const KParams & p, const MetCol & mc, const double * xin, int l, int col, const double * etal = nullptr) {
-	EdgeLev e;
-	const int L = p.L;
-	const int lc = l < 0 ? 0 : (l > L ? L : l);
-	const size_t NS = (size_t)p.NS;
-	e.we = xin[TMX_SLAB_W(L, lc) * NS + col];
-	metric_edge<MM>(p, mc, lc, col, e.ce0, e.ce1, e.ce2, etal);
-	return e;
-}
-
-struct ColConst { double c2a0, c2a1, c2b1, jn, je, drx, invdt, upc, cv; };
-
-// Values one block row shares with the next (level k quantities become level k-1 quantities, interface
-// k+1 quantities become interface k quantities).  Carrying them over instead of recomputing is the same
-// arithmetic on the same operands, so results stay bit-identical to the stand-alone evaluation.
-struct BlkCarry {
-	double ex, wn, xdn, ke;            // node k: Exner pressure, W on the level, xi_dot, kinetic energy
-	double ue, ve, xd, pe, re;         // interface k+1: U,V, xi_dot, rho*theta, rho interpolated
-};
-
-// block row k from node levels A = k-1, B = k, C = k+1 and interfaces a = k-1, b = k, c = k+1
-// column-operator coefficients from the LDS copy (ds_read: no vector-memory round trip, no vmcnt wait behind the U-row stores)
-// UD: the uniform-diffusion terms of BuildF (VerticalDynamicsFEM.cpp:2593-2635), udP = K_s / ztop^2 * second derivative
-// of (rho*theta - reference) on level k, udW = K_v / ztop^2 * the same for W on interface k, subtracted where the
-// reference subtracts them (before the upwinding terms); only the fully explicit mode evaluates them.
-// sign(x) * v as in the reference's upwinding terms ((x > 0) ? v : ((x < 0) ? -v : 0)), written as a chain of two selects: the
-// nested conditional became exec-masked branches, which cut the block row's assembly into short basic blocks
-__device__ __forceinline__ double signed_by(double x, double v) {
-	double r = 0.0;
-	r = (x < 0.0) ? -v : r;
-	r = (x > 0.0) ? v : r;
-	return r;
-}
-
-// INTERIOR: the caller guarantees 1 <= k <= L - 2 and arguments of the Exner function in the main range of exp / log (positive,
-// normal, finite): every level-boundary condition below is then a compile-time `true` and exp(log()) is evaluated without
-// branches (exner_from_rhotheta_bf), so that the whole block row is ONE basic block whose dependency chains the compiler can
-// interleave -- with the dozen short blocks of the general form a lone assembly wavefront ran at a quarter of its issue rate.
-// Same statements on the same operands either way.
-template <bool CARRY, bool UD = false, bool INTERIOR = false>
-__device__ __forceinline__ void compute_block(const KParams & p, const double * opsl, const ColConst & cc, int k,
-	const NodeLev & A, const NodeLev & B, const NodeLev & C, const EdgeLev & ea, const EdgeLev & eb, const EdgeLev & ec,
-	double * rowP, double * rowW, double * rowR, double & fP, double & fW, double & fR, BlkCarry & cy,
-	double udP = 0.0, double udW = 0.0, const double * rmtab = nullptr, long long * tseg = nullptr)
-{
-#ifdef TMX_PAIR_TIMING
-	long long ts_ = __builtin_readcyclecounter();
-#define CBSTAMP(i) do { if (tseg) { const long long t1_ = __builtin_readcyclecounter(); tseg[i] += t1_ - ts_; ts_ = t1_; } } while (0)
-#else
-#define CBSTAMP(i)
-#endif
-	const int L = p.L;
-#pragma unroll
-	for (int d = 0; d < TMX_BW; d++) { rowP[d] = 0.0; rowW[d] = 0.0; rowR[d] = 0.0; }
-	fP = 0.0; fW = 0.0; fR = 0.0;
-#define DOFF(cr, cc_, dk) (3 * (dk) + ((cc_) - (cr)) + 4)
-	// interior interpolation stencils (offsets -1, 0), verified by tmx_set_operators
-	const int kib = (INTERIOR || k < L) ? k : L;
-	const double ib_m = OPCL(TMX_OP_INTERP_NODE_TO_REDGE, kib, -1), ib_0 = OPCL(TMX_OP_INTERP_NODE_TO_REDGE, kib, 0);
-
-	// ---- interface k: interpolated U,V,rho*theta,rho and xi_dot (PrepareColumn :2056-2069) ----
-	double ue_b = 0.0, ve_b = 0.0, xd0 = 0.0, pe0 = 0.0, re0 = 0.0;
-	if (INTERIOR || (k >= 1 && k <= L - 1)) {
-		if (CARRY) { ue_b = cy.ue; ve_b = cy.ve; xd0 = cy.xd; pe0 = cy.pe; re0 = cy.re; }
-		else {
-			ue_b += ib_m * A.un; ue_b += ib_0 * B.un; ve_b += ib_m * A.vn; ve_b += ib_0 * B.vn;
-			xd0 = eb.ce0 * ue_b + eb.ce1 * ve_b + eb.ce2 * eb.we;
-			pe0 += ib_m * A.pn; pe0 += ib_0 * B.pn; re0 += ib_m * A.rn; re0 += ib_0 * B.rn;
-		}
-	}
-	// ---- interface k+1 ----
-	double ue_c = 0.0, ve_c = 0.0, xd1 = 0.0, pe1 = 0.0, re1 = 0.0;
-	double ic_m = 0.0, ic_0 = 0.0;
-	if (INTERIOR || k + 1 <= L - 1) {
-		ic_m = OPCL(TMX_OP_INTERP_NODE_TO_REDGE, k + 1, -1); ic_0 = OPCL(TMX_OP_INTERP_NODE_TO_REDGE, k + 1, 0);
-		ue_c += ic_m * B.un; ue_c += ic_0 * C.un; ve_c += ic_m * B.vn; ve_c += ic_0 * C.vn;
-		xd1 = ec.ce0 * ue_c + ec.ce1 * ve_c + ec.ce2 * ec.we;
-		pe1 += ic_m * B.pn; pe1 += ic_0 * C.pn; re1 += ic_m * B.rn; re1 += ic_0 * C.rn;
-	}
-
-	CBSTAMP(0);
-	if (INTERIOR || k < L) {
-		const double invJ = 1.0 / cc.jn;
-		const double pm = A.pn, p0 = B.pn, pp = C.pn, rm = A.rn, r0 = B.rn, rp = C.rn;
-		const double mf0 = (INTERIOR || k >= 1) ? cc.je * re0 * xd0 : 0.0, mf1 = (INTERIOR || k + 1 <= L - 1) ? cc.je * re1 * xd1 : 0.0;
-		const double pf0 = (INTERIOR || k >= 1) ? cc.je * pe0 * xd0 : 0.0, pf1 = (INTERIOR || k + 1 <= L - 1) ? cc.je * pe1 * xd1 : 0.0;
-		const double de0 = OPCL(TMX_OP_DIFF_REDGE_TO_NODE, k, 0), de1 = OPCL(TMX_OP_DIFF_REDGE_TO_NODE, k, 1);
-		double dmf = 0.0; dmf += de0 * mf0; dmf += de1 * mf1;
-		double dpf = 0.0; dpf += de0 * pf0; dpf += de1 * pf1;
-		fR = dmf * invJ;
-		fP += dpf * invJ;
-		if (UD) fP -= udP;
-		const double wlo = fabs(xd0), whi = fabs(xd1);
-		const double pl0 = OPCL(TMX_OP_PENALTY_LEFT, k, 0), pl1 = OPCL(TMX_OP_PENALTY_LEFT, k, 1);
-		const double pr0 = OPCL(TMX_OP_PENALTY_RIGHT, k, -1), pr1 = OPCL(TMX_OP_PENALTY_RIGHT, k, 0);
-		{
-			double a = 0.0;
-			if (INTERIOR || k < L - 1) { double b = 0.0; b += pl0 * p0; b += pl1 * pp; a += b * whi; }
-			if (INTERIOR || k > 0) { double b = 0.0; b += pr0 * pm; b += pr1 * p0; a += b * wlo; }
-			fP -= a;
-			a = 0.0;
-			if (INTERIOR || k < L - 1) { double b = 0.0; b += pl0 * r0; b += pl1 * rp; a += b * whi; }
-			if (INTERIOR || k > 0) { double b = 0.0; b += pr0 * rm; b += pr1 * r0; a += b * wlo; }
-			fR -= a;
-		}
-		// conservative flux terms: m = k (interface b), m = k+1 (interface c)
-		if (INTERIOR || k >= 1) {       // m = k, neither 0 nor L
-			const double c = de0 * cc.je * invJ * eb.ce2;
-			rowP[DOFF(0, 1, 0)] += c * pe0;
-			rowR[DOFF(2, 1, 0)] += c * re0;
-			const double cm = de0 * cc.je * invJ * ib_m * xd0, c0 = de0 * cc.je * invJ * ib_0 * xd0;
-			rowR[DOFF(2, 2, -1)] += cm; rowP[DOFF(0, 0, -1)] += cm;
-			rowR[DOFF(2, 2, 0)] += c0;  rowP[DOFF(0, 0, 0)] += c0;
-		}
-		if (INTERIOR || k + 1 <= L - 1) {   // m = k+1
-			const double c = de1 * cc.je * invJ * ec.ce2;
-			rowP[DOFF(0, 1, 1)] += c * pe1;
-			rowR[DOFF(2, 1, 1)] += c * re1;
-			const double cm = de1 * cc.je * invJ * ic_m * xd1, c0 = de1 * cc.je * invJ * ic_0 * xd1;
-			rowR[DOFF(2, 2, 0)] += cm; rowP[DOFF(0, 0, 0)] += cm;
-			rowR[DOFF(2, 2, 1)] += c0; rowP[DOFF(0, 0, 1)] += c0;
-		}
-		if (INTERIOR || k >= 1) {
-			const double sw = signed_by(xd0, eb.ce2);
-			rowP[DOFF(0, 1, 0)] -= sw * pr0 * pm; rowP[DOFF(0, 1, 0)] -= sw * pr1 * p0;
-			rowP[DOFF(0, 0, -1)] -= wlo * pr0;    rowP[DOFF(0, 0, 0)] -= wlo * pr1;
-			rowR[DOFF(2, 1, 0)] -= sw * pr0 * rm; rowR[DOFF(2, 1, 0)] -= sw * pr1 * r0;
-			rowR[DOFF(2, 2, -1)] -= wlo * pr0;    rowR[DOFF(2, 2, 0)] -= wlo * pr1;
-		}
-		if (INTERIOR || k + 1 <= L - 1) {
-			const double sw = signed_by(xd1, ec.ce2);
-			rowP[DOFF(0, 1, 1)] -= sw * pl0 * p0; rowP[DOFF(0, 1, 1)] -= sw * pl1 * pp;
-			rowP[DOFF(0, 0, 0)] -= whi * pl0;     rowP[DOFF(0, 0, 1)] -= whi * pl1;
-			rowR[DOFF(2, 1, 1)] -= sw * pl0 * r0; rowR[DOFF(2, 1, 1)] -= sw * pl1 * rp;
-			rowR[DOFF(2, 2, 0)] -= whi * pl0;     rowR[DOFF(2, 2, 1)] -= whi * pl1;
-		}
-	}
-
-	CBSTAMP(1);
-	// ---- node k quantities the W rows of this block and of the next one use ----
-	double ex0 = 0.0, wn0 = 0.0, xdn0 = 0.0, ke0 = 0.0;
-	if (INTERIOR || (k <= L - 1 && (CARRY || k >= 1))) {
-		ex0 = INTERIOR ? exner_from_rhotheta_bf(p, B.pn, rmtab) : (rmtab ? exner_from_rhotheta_lds(p, B.pn, rmtab) : exner_from_rhotheta(p, B.pn));
-		wn0 += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k, 0) * eb.we; wn0 += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k, 1) * ec.we;
-		xdn0 = B.ca2 * B.un + B.cb2 * B.vn + B.cx2 * wn0;
-		const double ca = cc.c2a0 * B.un + cc.c2a1 * B.vn + B.ca2 * wn0, cb = cc.c2a1 * B.un + cc.c2b1 * B.vn + B.cb2 * wn0;
-		ke0 = 0.5 * (ca * B.un + cb * B.vn + xdn0 * wn0);
-	}
-	CBSTAMP(2);
-	if (INTERIOR || (k >= 1 && k <= L - 1)) {
-		const double pm = A.pn, p0 = B.pn;
-		double exm, wnm, xdnm, kem;
-		if (CARRY) { exm = cy.ex; wnm = cy.wn; xdnm = cy.xdn; kem = cy.ke; }
-		else {
-			exm = rmtab ? exner_from_rhotheta_lds(p, pm, rmtab) : exner_from_rhotheta(p, pm);
-			wnm = 0.0; wnm += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k - 1, 0) * ea.we; wnm += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k - 1, 1) * eb.we;
-			xdnm = A.ca2 * A.un + A.cb2 * A.vn + A.cx2 * wnm;
-			const double ca = cc.c2a0 * A.un + cc.c2a1 * A.vn + A.ca2 * wnm, cb = cc.c2a1 * A.un + cc.c2b1 * A.vn + A.cb2 * wnm;
-			kem = 0.5 * (ca * A.un + cb * A.vn + xdnm * wnm);
-		}
-		(void)wnm;
-		const double pe = pe0, re = re0;
-		const double dnm = OPCL(TMX_OP_DIFF_NODE_TO_REDGE, k, -1), dn0 = OPCL(TMX_OP_DIFF_NODE_TO_REDGE, k, 0);
-		double dpe = 0.0; dpe += dnm * exm; dpe += dn0 * ex0;
-		const double unm = A.un, un0 = B.un, vnm = A.vn, vn0 = B.vn;
-		const double wem = ea.we, we0 = eb.we, wep = ec.we;
-		double dke = 0.0; dke += dnm * kem; dke += dn0 * ke0;
-		double dua = 0.0; dua += dnm * unm; dua += dn0 * un0;
-		double dub = 0.0; dub += dnm * vnm; dub += dn0 * vn0;
-		const double ue = ue_b, ve = ve_b;
-		const double cx0e = eb.ce0, cx1e = eb.ce1, cx2e = eb.ce2;
-		const double xde = xd0;
-		fW = dpe * pe / re;
-		fW += p.grav * cc.drx;
-		{
-			const double ca = cc.c2a0 * ue + cc.c2a1 * ve + cx0e * we0;
-			const double cb = cc.c2a1 * ue + cc.c2b1 * ve + cx1e * we0;
-			const double curl = -ca * dua - cb * dub;
-			fW += (dke + curl);
-		}
-		if (UD) fW -= udW;
-		const double ddm = OPCL(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, -1), dd0 = OPCL(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, 0), ddp = OPCL(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, 1);
-		double ddw = 0.0; ddw += ddm * wem; ddw += dd0 * we0; ddw += ddp * wep;
-		fW -= cc.upc * fabs(xde) * ddw;
-		const double cA = pe * p.Rd / (re * cc.cv);
-		rowW[DOFF(1, 0, -1)] += cA * dnm * exm / pm;
-		rowW[DOFF(1, 0, 0)] += cA * dn0 * ex0 / p0;
-		const double cB = 1.0 / (re * re) * dpe;
-		{
-			const double cC = cB * ib_m;
-			rowW[DOFF(1, 0, -1)] += cC * re;
-			rowW[DOFF(1, 2, -1)] += -cC * pe;
-		}
-		{
-			const double cC = cB * ib_0;
-			rowW[DOFF(1, 0, 0)] += cC * re;
-			rowW[DOFF(1, 2, 0)] += -cC * pe;
-		}
-		rowW[DOFF(1, 1, -1)] += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k - 1, 0) * dnm * xdnm;
-		rowW[DOFF(1, 1, 0)] += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k - 1, 1) * dnm * xdnm;
-		rowW[DOFF(1, 1, 0)] += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k, 0) * dn0 * xdn0;
-		rowW[DOFF(1, 1, 1)] += OPCL(TMX_OP_INTERP_REDGE_TO_NODE, k, 1) * dn0 * xdn0;
-		const double sw = signed_by(xde, cx2e);
-		rowW[DOFF(1, 1, 0)] -= cc.upc * sw * ddw;
-		rowW[DOFF(1, 1, -1)] -= cc.upc * fabs(xde) * ddm;
-		rowW[DOFF(1, 1, 0)] -= cc.upc * fabs(xde) * dd0;
-		rowW[DOFF(1, 1, 1)] -= cc.upc * fabs(xde) * ddp;
-	}
-	CBSTAMP(3);
-	rowP[4] += cc.invdt; rowW[4] += cc.invdt; rowR[4] += cc.invdt;
-	if (CARRY) {
-		cy.ex = ex0; cy.wn = wn0; cy.xdn = xdn0; cy.ke = ke0;
-		cy.ue = ue_c; cy.ve = ve_c; cy.xd = xd1; cy.pe = pe1; cy.re = re1;
-	}
-#undef DOFF
-#undef CBSTAMP
-}
-
+// The block row itself (NodeLev, EdgeLev, load_node, load_edge, ColConst, BlkCarry, compute_block): tmx_device_column.h.
 
 // one elimination step on the register window (dgbtf2 + forward substitution of dgbtrs), then slide.
 // U rows go to the HBM scratch for the back substitution.  Entries 4..8 of a row are fill-in that exists only
@@ -1834,256 +1598,6 @@ void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double
 #else
 	(void)lds; (void)sparse;
 #endif
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// VerticalDynamicsFEM::StepImplicitTermsExplicitly (src/atm/VerticalDynamicsFEM.cpp:439-612):
-// update -= dt * F(initial) for rho*theta, W, rho on EVERY column (F = BuildF of the initial column).
-
-// UD (fully explicit mode with uniform diffusion): F additionally holds the vertical diffusion of rho*theta and W
-// relative to the reference column xref (cs = K_s / ztop^2, cw = K_v / ztop^2).
-// UVX: the thread of (column, level k < L) also applies V.StepExplicit's update of U,V (v_explicit_point: penalty and, with UD,
-// the vertical diffusion), which reads the same U,V,W columns and metric rows -- one launch less per stage and the operands
-// found in the cache
-template <bool UD, bool UVX>
-// KT_VC levels per workgroup.  A thread reads the levels k-2 .. k+2 of its column, so the level tiles of a column overlap by
-// four levels and every value is fetched 2.7 times over at the L2's memory side (PMC, ne30 L40: 514 MB of reads per launch for
-// 190 MB of operands: the level-neighbour tiles are 1 350 workgroups apart in dispatch order, on another XCD's L2).  Taller
-// tiles make the neighbours wavefronts of one workgroup, and lose: config 4's step takes 5.12 / 5.21 / 5.34 ms with 4 / 8 / 16
-// levels per workgroup (1 024-thread workgroups leave one per CU).  4 stays.
-#ifndef KT_VC
-#define KT_VC 4
-#endif
-__global__ __launch_bounds__(64 * KT_VC) void k_vi_terms_explicit(KParams p, const double * __restrict__ xin,
-	double * __restrict__ xup, double dt, const double * __restrict__ xref, double cs, double cw, int ntile, int xmode)
-{
-	const int L = p.L;
-	const size_t NS = (size_t)p.NS;
-	int bx, by;
-	if (!xcd_column_tile(xmode, ntile, (L + 1 + KT_VC - 1) / KT_VC, bx, by)) return;
-	const int col = (p.quads ? p.quads[bx] : bx) * 64 + threadIdx.x;
-	const int k = by * KT_VC + WAVE_UNIFORM(threadIdx.y);
-	if (col >= p.ncol || k > L) return;
-	ColConst cc;
-	cc.c2a0 = p.g2d[G2_C2A0 * NS + col]; cc.c2a1 = p.g2d[G2_C2A1 * NS + col]; cc.c2b1 = p.g2d[G2_C2B1 * NS + col];
-	cc.jn = p.g2d[G2_JN * NS + col]; cc.je = p.g2d[G2_JE * NS + col]; cc.drx = p.g2d[G2_DRX * NS + col];
-	cc.invdt = 1.0 / dt; cc.upc = 0.5 * (1.0 / (double)L); cc.cv = p.cp - p.Rd;
-	const MetCol mcol = met_col(p, col);
-	// the values to update, loaded with the operands (at the point of use their latency would follow the whole evaluation)
-	const double upW = xup[TMX_SLAB_W(L, k) * NS + col];
-	const double upT = (k < L) ? xup[TMX_SLAB_T(L, k) * NS + col] : 0.0, upR = (k < L) ? xup[TMX_SLAB_R(L, k) * NS + col] : 0.0;
-	const NodeLev nA = load_node(p, mcol, xin, k - 1, col), nB = load_node(p, mcol, xin, k, col), nC = load_node(p, mcol, xin, k + 1, col);
-	const EdgeLev eA = load_edge(p, mcol, xin, k - 1, col), eB = load_edge(p, mcol, xin, k, col), eC = load_edge(p, mcol, xin, k + 1, col);
-	double rP[TMX_BW], rW[TMX_BW], rR[TMX_BW], fP, fW, fR;
-	BlkCarry cy;
-	double udP = 0.0, udW = 0.0;
-	if (UD) {
-		// PrepareColumn :2104-2160: DiffDiff of the column minus DiffDiff of the reference column; W not on the boundaries
-		if (k < L) {
-			double dd = 0.0, ddr = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 2; off++) {
-				const int l = k + off;
-				if (l < 0 || l >= L) continue;
-				const double c = OPC(TMX_OP_DIFFDIFF_NODE_TO_NODE, k, off);
-				dd += c * xin[(size_t)TMX_SLAB_T(L, l) * NS + col];
-				ddr += c * xref[(size_t)TMX_SLAB_T(L, l) * NS + col];
-			}
-			udP = cs * (dd - ddr);
-		}
-		if (k > 0 && k < L) {
-			double dd = 0.0, ddr = 0.0;
-#pragma unroll
-			for (int off = -2; off <= 2; off++) {
-				const int l = k + off;
-				if (l < 0 || l > L) continue;
-				const double c = OPC(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, off);
-				dd += c * xin[(size_t)TMX_SLAB_W(L, l) * NS + col];
-				ddr += c * xref[(size_t)TMX_SLAB_W(L, l) * NS + col];
-			}
-			udW = cw * (dd - ddr);
-		}
-	}
-	compute_block<false, UD>(p, p.ops, cc, k, nA, nB, nC, eA, eB, eC, rP, rW, rR, fP, fW, fR, cy, udP, udW);
-	if (k < L) {
-		xup[TMX_SLAB_T(L, k) * NS + col] = upT - dt * fP;
-		xup[TMX_SLAB_R(L, k) * NS + col] = upR - dt * fR;
-	}
-	xup[TMX_SLAB_W(L, k) * NS + col] = upW - dt * fW;
-	if (UVX && k < L) v_explicit_point<UD>(p, xin, xup, dt, xref, cw, col, k);
-}
-
-// The same update by a thread that walks a column (or one of `nseg` segments of it) block row by block row, as the column solve's
-// assembly does: the three node levels and three interfaces a block row touches in a sliding register window, the quantities a
-// block row shares with the next carried over (compute_block<CARRY>: one evaluation of the Exner function per level instead of
-// two, every state value loaded once instead of three to five times), the next levels loaded two iterations ahead, operator
-// coefficients and the 1 - eta table in LDS.  The uniform-diffusion stencils take the state's five levels from the window (the
-// value that has just left it, the three in it, the one about to enter) and keep sliding windows of the reference's.  A segment that
-// does not start at the bottom evaluates the block row below it first, only to fill the carry.  Same statements on the same
-// operands as k_vi_terms_explicit: bit-identical (tested).
-template <bool UD, bool CLOSED>
-__global__ __launch_bounds__(128) void k_vi_terms_explicit_slide(KParams p, const double * __restrict__ xin,
-	double * __restrict__ xup, double dt, const double * __restrict__ xref, double cs, double cw, int ntile, int xmode, int nseg)
-{
-	extern __shared__ double opsl_mem[];
-	double * opsl = opsl_mem;
-	const int L = p.L;
-	constexpr int MM = CLOSED ? 1 : 2;
-	double * etal = opsl_mem + TMX_OP_COUNT * (L + 1) * TMX_OPW;
-	// the exp / log tables of the Exner function in LDS too: read from global memory each lookup is a vector-memory load behind an
-	// s_waitcnt vmcnt(0), i.e. two waits per block row for every level prefetch in flight (the column solve's assembly: the same)
-	double * rmtab = etal + 2 * L + 1;
-	walk_tables_to_lds<CLOSED>(p, opsl, etal);
-	tmx_rm_tables_to_lds(rmtab, threadIdx.y * 64 + threadIdx.x, 128);
-	__syncthreads();
-	const size_t NS = (size_t)p.NS;
-	int col, k0, k1;      // block rows k0 .. k1 - 1 of 0 .. L
-	if (!walk_segment(p, xmode, ntile, nseg, L + 1, col, k0, k1)) return;
-	ColConst cc;
-	cc.c2a0 = p.g2d[G2_C2A0 * NS + col]; cc.c2a1 = p.g2d[G2_C2A1 * NS + col]; cc.c2b1 = p.g2d[G2_C2B1 * NS + col];
-	cc.jn = p.g2d[G2_JN * NS + col]; cc.je = p.g2d[G2_JE * NS + col]; cc.drx = p.g2d[G2_DRX * NS + col];
-	cc.invdt = 1.0 / dt; cc.upc = 0.5 * (1.0 / (double)L); cc.cv = p.cp - p.Rd;
-	const MetCol mcol = met_col(p, col);
-	const int kw = (k0 > 0) ? k0 - 1 : 0;      // first block row evaluated (k0 - 1: for the carry only)
-	// The window: block row k reads U, V, rho*theta, rho of the levels k - 1, k, k + 1 and W of the interfaces k - 1, k, k + 1; with the
-	// carry, the metric terms of level k and of the interfaces k, k + 1 only.  Levels k + 2 and k + 3 are in flight as raw values
-	// (their metric terms are arithmetic on per-column factors and the LDS table: evaluated when a level becomes the window's top).
-	struct Raw { double un, vn, pn, rn, we; };
-	auto raw = [&](int l) {      // (out-of-range levels carry the values of the nearest one, as load_node / load_edge)
-		Raw r;
-		const int lc = l < 0 ? 0 : (l >= L ? L - 1 : l), le = l < 0 ? 0 : (l > L ? L : l);
-		r.un = xin[TMX_SLAB_U(L, lc) * NS + col]; r.vn = xin[TMX_SLAB_V(L, lc) * NS + col];
-		r.pn = xin[TMX_SLAB_T(L, lc) * NS + col]; r.rn = xin[TMX_SLAB_R(L, lc) * NS + col];
-		r.we = xin[TMX_SLAB_W(L, le) * NS + col];
-		return r;
-	};
-	auto node_of = [&](const Raw & r, int l) {
-		NodeLev n; n.un = r.un; n.vn = r.vn; n.pn = r.pn; n.rn = r.rn;
-		const int lc = l < 0 ? 0 : (l >= L ? L - 1 : l);
-		metric_node3<MM>(p, mcol, lc, col, n.ca2, n.cb2, n.cx2, etal);
-		return n;
-	};
-	auto edge_of = [&](const Raw & r, int l) {
-		EdgeLev e; e.we = r.we;
-		const int le = l < 0 ? 0 : (l > L ? L : l);
-		metric_edge<MM>(p, mcol, le, col, e.ce0, e.ce1, e.ce2, etal);
-		return e;
-	};
-	Raw rA = raw(kw - 1), rN = raw(kw + 2);
-	NodeLev nB = load_node<MM>(p, mcol, xin, kw, col, etal), nC = load_node<MM>(p, mcol, xin, kw + 1, col, etal);
-	EdgeLev eB = load_edge<MM>(p, mcol, xin, kw, col, etal), eC = load_edge<MM>(p, mcol, xin, kw + 1, col, etal);
-	double pm2 = 0.0, wm2 = 0.0;      // rho*theta of level k - 2, W of interface k - 2 (what has left the window)
-	double tr[5] = { 0, 0, 0, 0, 0 }, wr[5] = { 0, 0, 0, 0, 0 };      // reference rho*theta on the levels, W on the interfaces k - 2 .. k + 2
-	auto ref_T = [&](int l) { return (UD && l >= 0 && l < L) ? xref[(size_t)TMX_SLAB_T(L, l) * NS + col] : 0.0; };
-	auto ref_W = [&](int l) { return (UD && l >= 0 && l <= L) ? xref[(size_t)TMX_SLAB_W(L, l) * NS + col] : 0.0; };
-	if (UD) {
-		if (kw - 2 >= 0) { pm2 = xin[(size_t)TMX_SLAB_T(L, kw - 2) * NS + col]; wm2 = xin[(size_t)TMX_SLAB_W(L, kw - 2) * NS + col]; }
-#pragma unroll
-		for (int t = 0; t < 5; t++) { tr[t] = ref_T(kw - 2 + t); wr[t] = ref_W(kw - 2 + t); }
-	}
-	double upT = 0.0, upR = 0.0, upW = 0.0;
-	if (kw == k0) {
-		upW = xup[TMX_SLAB_W(L, kw) * NS + col];
-		if (kw < L) { upT = xup[TMX_SLAB_T(L, kw) * NS + col]; upR = xup[TMX_SLAB_R(L, kw) * NS + col]; }
-	}
-	BlkCarry cy = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-#pragma unroll 1
-	for (int k = kw; k < k1; k++) {
-		// two levels ahead: the level that enters the window after the next block row; the reference's entering values and the
-		// values the next block row updates
-		const Raw rNN = raw(k + 3);
-		const double trn = ref_T(k + 3), wrn = ref_W(k + 3);
-		double upTn = 0.0, upRn = 0.0, upWn = 0.0;
-		if (k + 1 < k1) {
-			upWn = xup[TMX_SLAB_W(L, k + 1) * NS + col];
-			if (k + 1 < L) { upTn = xup[TMX_SLAB_T(L, k + 1) * NS + col]; upRn = xup[TMX_SLAB_R(L, k + 1) * NS + col]; }
-		}
-		double udP = 0.0, udW = 0.0;
-		if (UD) {
-			const double tw[5] = { pm2, rA.pn, nB.pn, nC.pn, rN.pn }, ww[5] = { wm2, rA.we, eB.we, eC.we, rN.we };
-			if (k < L) {
-				double dd = 0.0, ddr = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 2; off++) {
-					const int l = k + off;
-					if (l < 0 || l >= L) continue;
-					const double c = OPCL(TMX_OP_DIFFDIFF_NODE_TO_NODE, k, off);
-					dd += c * tw[off + 2];
-					ddr += c * tr[off + 2];
-				}
-				udP = cs * (dd - ddr);
-			}
-			if (k > 0 && k < L) {
-				double dd = 0.0, ddr = 0.0;
-#pragma unroll
-				for (int off = -2; off <= 2; off++) {
-					const int l = k + off;
-					if (l < 0 || l > L) continue;
-					const double c = OPCL(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, off);
-					dd += c * ww[off + 2];
-					ddr += c * wr[off + 2];
-				}
-				udW = cw * (dd - ddr);
-			}
-		}
-		double rP[TMX_BW], rW[TMX_BW], rR[TMX_BW], fP, fW, fR;
-		{
-			NodeLev nA; nA.un = rA.un; nA.vn = rA.vn; nA.pn = rA.pn; nA.rn = rA.rn; nA.ca2 = 0.0; nA.cb2 = 0.0; nA.cx2 = 0.0;      // (with the carry a block row reads no metric term of level k - 1)
-			EdgeLev eA; eA.we = rA.we; eA.ce0 = 0.0; eA.ce1 = 0.0; eA.ce2 = 0.0;
-			compute_block<true, UD>(p, opsl, cc, k, nA, nB, nC, eA, eB, eC, rP, rW, rR, fP, fW, fR, cy, udP, udW, rmtab);
-		}
-		const double resT = upT - dt * fP, resR = upR - dt * fR, resW = upW - dt * fW;
-		pm2 = rA.pn; wm2 = rA.we;
-		rA.un = nB.un; rA.vn = nB.vn; rA.pn = nB.pn; rA.rn = nB.rn; rA.we = eB.we;
-		nB = nC; eB = eC;
-		nC = node_of(rN, k + 2); eC = edge_of(rN, k + 2);
-		rN = rNN;
-		tr[0] = tr[1]; tr[1] = tr[2]; tr[2] = tr[3]; tr[3] = tr[4]; tr[4] = trn;
-		wr[0] = wr[1]; wr[1] = wr[2]; wr[2] = wr[3]; wr[3] = wr[4]; wr[4] = wrn;
-		upT = upTn; upR = upRn; upW = upWn;
-		// The block row's stores LAST, behind the window's move (which evaluates the metric terms of the level that enters, i.e. reads values
-		// loaded an iteration ago): the stores sit in a branch, the compiler cannot count them, and a loaded value first used behind them waits
-		// for everything in flight -- the stores' own completion and the prefetch of two levels ahead -- once per block row.  The values the
-		// next block row updates are made to land before the stores too (they were loaded with this block row's operands).
-		asm volatile("" : "+v"(upT), "+v"(upR), "+v"(upW));
-		if (k >= k0) {
-			if (k < L) {
-				xup[TMX_SLAB_T(L, k) * NS + col] = resT;
-				xup[TMX_SLAB_R(L, k) * NS + col] = resR;
-			}
-			xup[TMX_SLAB_W(L, k) * NS + col] = resW;
-		}
-	}
-}
-
-void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv) {
-	const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
-	const size_t lds_slide = walk_lds_bytes(p.L, TMX_RMTAB_DOUBLES);
-	if (e->opt_vite_walk < 0 && !with_uv && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
-		const int nseg = walk_segments(e->opt_vite_walk, nt_, p.L + 1, 2048);
-		dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
-		const bool ud = e->udiff && e->fully_explicit;
-		const double z2 = e->cfg.ztop * e->cfg.ztop;
-		const double cs = ud ? e->cfg.uniform_diffusion_scalar / z2 : 0.0, cw = ud ? e->cfg.uniform_diffusion_vector / z2 : 0.0;
-#define LAUNCH_VS(UD_, CL_) hipLaunchKernelGGL((k_vi_terms_explicit_slide<UD_, CL_>), grd, blk, lds_slide, e->stream, p, xin, xup, dt, (const double *)(ud ? e->d_ref : nullptr), cs, cw, nt_, xm, nseg)
-		if (ud) { if (p.closed) LAUNCH_VS(true, true); else LAUNCH_VS(true, false); }
-		else { if (p.closed) LAUNCH_VS(false, true); else LAUNCH_VS(false, false); }
-#undef LAUNCH_VS
-		return;
-	}
-	dim3 blk(64, KT_VC), grd(xcd_column_grid(xm, nt_, (p.L + 1 + KT_VC - 1) / KT_VC));
-	if (e->udiff && e->fully_explicit) {
-		const double z2 = e->cfg.ztop * e->cfg.ztop;
-#if TMX_EXP      // (option "vx_fused", measured slower: experiments flavour only)
-		if (with_uv) hipLaunchKernelGGL((k_vi_terms_explicit<true, true>), grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)e->d_ref,
-			e->cfg.uniform_diffusion_scalar / z2, e->cfg.uniform_diffusion_vector / z2, nt_, xm);
-		else
-#endif
-		hipLaunchKernelGGL((k_vi_terms_explicit<true, false>), grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)e->d_ref,
-			e->cfg.uniform_diffusion_scalar / z2, e->cfg.uniform_diffusion_vector / z2, nt_, xm);
-	} else
-		hipLaunchKernelGGL((k_vi_terms_explicit<false, false>), grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)nullptr, 0.0, 0.0, nt_, xm);
 }
 
 }      // namespace lu_fma / lu_nofma

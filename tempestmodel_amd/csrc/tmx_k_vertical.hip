@@ -13,16 +13,14 @@
 // order of the reference (which is built without FMA contraction).
 //
 // Reference behaviour restated (file:line under the reference tree) is cited per kernel.
-#include "tmx_device.h"
-
-// Both flavours of the band LU live in ONE library: this translation unit is compiled twice -- as it stands (LU updates fused, what OpenBLAS
-// and MKL's FMA code paths compute) and with -DTMX_LU_NOFMA (multiply and subtract rounded separately, a BLAS without fused multiply-adds:
-// tmx_device.h, LU_UPD) -- into a namespace each; tmx_lu_select.hip dispatches by the engine's option "lu_fma" (tmx_set_option, any time).
-#ifdef TMX_LU_NOFMA
-namespace lu_nofma {
-#else
-namespace lu_fma {
-#endif
+//
+// This unit holds the vertical kernels WITHOUT a band LU, i.e. that never use LU_UPD (tmx_device.h): V.StepExplicit (k_v_explicit,
+// k_v_explicit_slide), the explicit column update of the tracers (k_v_tracers_explicit_column / _tile / _slide; its "solve" is a
+// division by the diagonal), the negative-tracer filter (k_v_filter_tracers) and StepImplicitTermsExplicitly (k_vi_terms_explicit,
+// k_vi_terms_explicit_slide: the column solve's block-row assembly, tmx_device_column.h, evaluated for F only).  It is compiled once
+// and its launchers are called directly.  The kernels that hold the LU are compiled in both of its roundings: tmx_k_column.hip (the
+// column solve) and tmx_k_tracer_solve.hip (the implicit column update of the tracers), dispatched by tmx_lu_select.hip.
+#include "tmx_device_column.h"
 
 template <bool UDV>
 __global__ __launch_bounds__(64 * KT_VE) void k_v_explicit(KParams p, const double * __restrict__ xin,
@@ -143,426 +141,88 @@ void tmxk_v_explicit(tmx_engine * e, const KParams & p, const double * xin, doub
 		hipLaunchKernelGGL(k_v_explicit<false>, grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)nullptr, 0.0, nt_, xm);
 }
 
-// VerticalDynamicsFEM::UpdateColumnTracers (VerticalDynamicsFEM.cpp:3783-4282), implicit mode, vertical order 1:
-// one lane per unique column.  The tridiagonal matrix (kl = ku = 1) is kept in LAPACK band storage
-// AB(i, j) = sm[(j * 4 + 2 + i - j)] and factorised / solved with the dgbtf2 / dgbtrs loops (first-maximum
-// pivoting, column-oriented back substitution) -- the restatement oracle/tmx_oracle.c:orc_dgbsv pins against
-// LAPACK -- once per tracer on a fresh copy, which is what dgbtrf + dgbtrs per tracer compute.
-// xin: initial instance (U, V, tracer densities), w0: W of the initial column [L+1][NS] (a saved copy when the step
-// runs in place and the state kernel has already overwritten it), xup: update instance (updated W; receives the tracers),
-// xbase: instance holding the tracer values the update is subtracted from (the update instance itself in the
-// reference; the initial instance when the preceding CopyData was fused away).
-// expl (fully explicit vertical mode, :3910-3912, :4047-4063, :4117-4141, :4166-4170, :4193): every stored column is
-// advanced on its own (ucol == udep == nullptr; the update instance has not been through the DSS yet), the matrix is
-// the diagonal 1/dt (dgbtrs then is one division per level), xi_dot comes from the initial W for both uses, there
-// is no velocity correction, and with ks != 0 the mass flux carries the uniform diffusion of q / rho - (q / rho)_ref.
-// LW = columns per workgroup (the lane stride of the LDS arrays): 64, or 32 when (8L + 2) x 512 bytes exceed the 160 KB of a
-// CU (L >= 40, e.g. the 40 levels of the DCMIP2016 supercell) -- half-filled wavefronts, twice the workgroups.
+// VerticalDynamicsFEM::UpdateColumnTracers (VerticalDynamicsFEM.cpp:3783-4282) in the fully explicit vertical mode (:3910-3912,
+// :4047-4063, :4117-4141, :4166-4170, :4193), one lane per stored column, the column's operands in LDS (option "vt_column": the
+// cross-check of the level-parallel and column-walking forms below).  Every stored column is advanced on its own, in place on the
+// update instance (which has not been through the DSS yet); the matrix is the diagonal 1/dt (dgbtrs then is one division per level:
+// tracer_explicit_solve, no band LU), xi_dot comes from the initial W for the flux and for the upwinding alike, there is no velocity
+// correction, and with ks != 0 the mass flux carries the uniform diffusion of q / rho - (q / rho)_ref.
+// LW = columns per workgroup (the lane stride of the LDS arrays): 64, or 32 -- half-filled wavefronts, twice the workgroups -- where
+// 64 columns do not fit a CU (vt_explicit_column_lds).
 template <int LW>
-__global__ __launch_bounds__(64) void k_vi_tracers(KParams p, int nt, const double * __restrict__ xin, const double * __restrict__ w0,
-	const double * xbase, double * xup, double dt, int nunique, const int * __restrict__ ucol, const int * __restrict__ udep, int * __restrict__ flag,
-	int expl, double ks, const double * __restrict__ xref)
+__global__ __launch_bounds__(64) void k_v_tracers_explicit_column(KParams p, int nt, const double * __restrict__ xin, double * xup, double dt,
+	double ks, const double * __restrict__ xref)
 {
 	extern __shared__ double smt[];
 	const int L = p.L, lane = threadIdx.x;
 	const size_t NS = (size_t)p.NS;
-	double * A = smt;                        // [L][4][LW] band matrix, rebuilt and factorised per tracer
-	double * F = A + (size_t)L * 4 * LW;     // [L][LW] right-hand side / solution
-	double * xd0 = F + (size_t)L * LW;       // [L+1][LW] xi_dot of the initial column on interfaces
-	double * xd1 = xd0 + (size_t)(L + 1) * LW;   // [L+1][LW] xi_dot with the updated W
-	double * qn = xd1 + (size_t)(L + 1) * LW;    // [L][LW] tracer density of the column
-	const int u = blockIdx.x * LW + lane;
-	if (lane >= LW || u >= nunique) return;
-	const int col = ucol ? ucol[u] : u;
+	double * xd0 = smt;                            // [L+1][LW] xi_dot of the initial column on interfaces
+	double * rhoe = xd0 + (size_t)(L + 1) * LW;    // [L+1][LW] rho on interfaces (uniform diffusion only)
+	double * qn = rhoe + (size_t)(L + 1) * LW;     // [L][LW] tracer density of the column
+	double * mixr = qn + (size_t)L * LW;           // [L][LW] q / rho - (q / rho)_ref (uniform diffusion only)
+	const int col = blockIdx.x * LW + lane;
+	if (lane >= LW || col >= p.ncol) return;
 	const MetCol mc = met_col(p, col);
 	const double jn = p.g2d[G2_JN * NS + col], je = p.g2d[G2_JE * NS + col];
-	double * mixr = A;                       // explicit mode: [L][LW] q / rho - (q / rho)_ref   (the matrix is not stored)
-	double * rhoe = A + (size_t)L * LW;      // explicit mode: [L+1][LW] rho on interfaces
-#define ABW(i_, j_) A[((size_t)(j_) * 4 + 2 + (i_) - (j_)) * LW + lane]
-	// U,V on interfaces (InterpolateNodeToREdge of the initial column), xi_dot initial / updated (:3943-3957, :4059-4086)
+	const double * w0 = xin + (size_t)TMX_SLAB_W(L, 0) * NS;
+	// U,V on interfaces (InterpolateNodeToREdge of the initial column), xi_dot (:3943-3957)
 	for (int k = 0; k <= L; k++) {
-		double x0v = 0.0, x1v = 0.0;
+		double x0v = 0.0;
 		if (k >= 1 && k <= L - 1) {
 			const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_U(L, k + off) * NS + col]; });
 			const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_V(L, k + off) * NS + col]; });
 			double e0, e1, e2;
 			metric_edge(p, mc, k, col, e0, e1, e2);
 			x0v = e0 * ue + e1 * ve + e2 * w0[(size_t)k * NS + col];
-			x1v = expl ? x0v : e0 * ue + e1 * ve + e2 * xup[(size_t)TMX_SLAB_W(L, k) * NS + col];
 		}
-		xd0[(size_t)k * LW + lane] = x0v; xd1[(size_t)k * LW + lane] = x1v;
+		xd0[(size_t)k * LW + lane] = x0v;
 	}
-	// The matrix (the same for every tracer; the reference factorises it once) is cheap to rebuild from xi_dot, which
-	// keeps the LDS footprint at (8L + 2) x 512 bytes.
-	auto assemble = [&]() {
-		for (int t = 0; t < L * 4; t++) A[(size_t)t * LW + lane] = 0.0;
-		// d F_k / d q_n: DiffREdgeToNode x J_e / J_n x InterpNodeToREdge x xi_dot (:3959-3976); J is level-independent
-		for (int k = 0; k < L; k++)
-			for (int mo = 0; mo <= 1; mo++) {
-				const int m = k + mo;                          // DiffREdgeToNode row k touches interfaces k, k+1
-				const double dc = OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, mo);
-				for (int no = -2; no <= 1; no++) {
-					const int n = m + no;                      // InterpNodeToREdge row m: nodes m-1, m (two-sided at the ends)
-					if (n < 0 || n >= L) continue;
-					if (n - k < -1 || n - k > 1) continue;     // outside the band the coefficient is structurally zero
-					ABW(k, n) += dc * je / jn * OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, no) * xd0[(size_t)m * LW + lane];
-				}
-			}
-		// upwinding in the Jacobian (:3978-4016): interface a, weight |xi_dot_a|
-		for (int a = 1; a < L; a++) {
-			const double wgt = fabs(xd0[(size_t)a * LW + lane]);
-			ABW(a - 1, a - 1) -= wgt * OPC(TMX_OP_PENALTY_LEFT, a - 1, 0);
-			ABW(a - 1, a) -= wgt * OPC(TMX_OP_PENALTY_LEFT, a - 1, 1);
-			ABW(a, a - 1) -= wgt * OPC(TMX_OP_PENALTY_RIGHT, a, -1);
-			ABW(a, a) -= wgt * OPC(TMX_OP_PENALTY_RIGHT, a, 0);
-		}
-		for (int k = 0; k < L; k++) ABW(k, k) += 1.0 / dt;
-	};
-
-	int dep[3];
-#pragma unroll
-	for (int t = 0; t < 3; t++) dep[t] = udep ? udep[u * 3 + t] : -1;
-	bool singular = false, factored = false;
-	unsigned long long jpmask = 0, jpmask_hi = 0, zeromask = 0, zeromask_hi = 0;      // interchanges / zero pivots of the factorisation, by column
-	if (expl && ks != 0.0) {
+	if (ks != 0.0) {
 		// rho on interfaces: InterpolateNodeToREdge of the initial column (PrepareColumn :1905-1916)
 		for (int m = 0; m <= L; m++)
 			rhoe[(size_t)m * LW + lane] = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, m, [&](int off) { return xin[(size_t)TMX_SLAB_R(L, m + off) * NS + col]; });
 	}
+	const double idt = 1.0 / dt;
+	auto xd = [&](int m) { return xd0[(size_t)m * LW + lane]; };
 	for (int c = 0; c < nt; c++) {
 		for (int k = 0; k < L; k++) qn[(size_t)k * LW + lane] = xin[(size_t)TMX_SLAB_Q(L, c, k) * NS + col];
-		if (expl && ks != 0.0)
+		if (ks != 0.0)
 			for (int k = 0; k < L; k++) {
 				double a = qn[(size_t)k * LW + lane] / xin[(size_t)TMX_SLAB_R(L, k) * NS + col];
 				a -= xref[(size_t)TMX_SLAB_Q(L, c, k) * NS + col] / xref[(size_t)TMX_SLAB_R(L, k) * NS + col];
 				mixr[(size_t)k * LW + lane] = a;
 			}
-		// mass flux with the updated xi_dot, its divergence (:4092-4140), upwinding with the initial xi_dot (:4153-4181): tracer_rhs_level
-		for (int k = 0; k < L; k++)
-			F[(size_t)k * LW + lane] = tracer_rhs_level(p.ops, L, k, je, jn, expl && ks != 0.0, ks,
-				[&](int l) { return qn[(size_t)l * LW + lane]; }, [&](int l) { return mixr[(size_t)l * LW + lane]; },
-				[&](int m) { return xd1[(size_t)m * LW + lane]; }, [&](int m) { return xd0[(size_t)m * LW + lane]; }, [&](int m) { return rhoe[(size_t)m * LW + lane]; });
-		if (expl) {
-			// diagonal matrix 1/dt: dgbtrs leaves b_j / (1/dt)
-			const double idt = 1.0 / dt;
-			for (int k = 0; k < L; k++) {
-				const size_t so = (size_t)TMX_SLAB_Q(L, c, k) * NS;
-				xup[so + col] = xbase[so + col] - tracer_explicit_solve(F[(size_t)k * LW + lane], idt);
-			}
-			continue;
-		}
-		// implicit velocity correction (:4183-4233)
-		for (int a = 1; a < L; a++) {
-			const double xa = xd0[(size_t)a * LW + lane];
-			double e0, e1, e2;
-			metric_edge(p, mc, a, col, e0, e1, e2);
-			const double sw = (xa > 0.0) ? 1.0 * e2 : ((xa < 0.0) ? -1.0 * e2 : 0.0);
-			const double jump = sw * (xup[(size_t)TMX_SLAB_W(L, a) * NS + col] - w0[(size_t)a * NS + col]);
-			double f = F[(size_t)(a - 1) * LW + lane];
-			f -= OPC(TMX_OP_PENALTY_LEFT, a - 1, 0) * qn[(size_t)(a - 1) * LW + lane] * jump;
-			f -= OPC(TMX_OP_PENALTY_LEFT, a - 1, 1) * qn[(size_t)a * LW + lane] * jump;
-			F[(size_t)(a - 1) * LW + lane] = f;
-			f = F[(size_t)a * LW + lane];
-			f -= OPC(TMX_OP_PENALTY_RIGHT, a, -1) * qn[(size_t)(a - 1) * LW + lane] * jump;
-			f -= OPC(TMX_OP_PENALTY_RIGHT, a, 0) * qn[(size_t)a * LW + lane] * jump;
-			F[(size_t)a * LW + lane] = f;
-		}
-		// dgbtf2 (kl = ku = 1, kv = 2) once per column -- the matrix is the same for every tracer, the reference factorises it
-		// once (:4028-4040) --, then per tracer dgbtrs: forward substitution with the stored multipliers and interchanges, dtbsv
-		if (!factored) {
-			factored = true;
-			assemble();
-			int ju = 0;
-			for (int jj = 0; jj < L; jj++) {
-				if (jj + 2 < L) ABW(jj + 2 - 2, jj + 2) = 0.0;         // fill-in super-diagonal of column jj + kv
-				const int km = (jj < L - 1) ? 1 : 0;
-				int jp = 0;
-				if (km && fabs(ABW(jj + 1, jj)) > fabs(ABW(jj, jj))) jp = 1;
-				const double piv = ABW(jj + jp, jj);
-				if (piv != 0.0) {
-					int tt = jj + 1 + jp; if (tt > L - 1) tt = L - 1;
-					if (tt > ju) ju = tt;
-					if (jp) {
-						jpmask |= 1ull << (jj & 63); if (jj >= 64) jpmask_hi |= 1ull << (jj - 64);
-						for (int cc = jj; cc <= ju; cc++) { const double tmp = ABW(jj + 1, cc); ABW(jj + 1, cc) = ABW(jj, cc); ABW(jj, cc) = tmp; }
-					}
-					if (km) {
-						const double r = 1.0 / ABW(jj, jj);
-						ABW(jj + 1, jj) *= r;
-						for (int cc = jj + 1; cc <= ju; cc++) {
-							const double uu = ABW(jj, cc);
-							if (uu != 0.0) ABW(jj + 1, cc) = LU_UPD(ABW(jj + 1, cc), ABW(jj + 1, jj), uu);
-						}
-					}
-				} else { singular = true; zeromask |= 1ull << (jj & 63); if (jj >= 64) zeromask_hi |= 1ull << (jj - 64); }
-			}
-		}
-		// forward substitution (dgbtrs): interchange, then eliminate; a zero pivot leaves its column untouched, as above
-		for (int jj = 0; jj < L - 1; jj++) {
-			const unsigned long long bit = 1ull << (jj & 63);
-			const bool isz = (jj < 64) ? (zeromask & bit) != 0 : (zeromask_hi & (1ull << (jj - 64))) != 0;
-			if (isz) continue;
-			const bool jp = (jj < 64) ? (jpmask & bit) != 0 : (jpmask_hi & (1ull << (jj - 64))) != 0;
-			if (jp) { const double tmp = F[(size_t)(jj + 1) * LW + lane]; F[(size_t)(jj + 1) * LW + lane] = F[(size_t)jj * LW + lane]; F[(size_t)jj * LW + lane] = tmp; }
-			F[(size_t)(jj + 1) * LW + lane] = LU_UPD(F[(size_t)(jj + 1) * LW + lane], F[(size_t)jj * LW + lane], ABW(jj + 1, jj));
-		}
-		for (int jj = L - 1; jj >= 0; jj--) {
-			double bj = F[(size_t)jj * LW + lane];
-			if (bj != 0.0) {
-				bj /= ABW(jj, jj);
-				F[(size_t)jj * LW + lane] = bj;
-				const int lo = (jj - 2 < 0) ? 0 : jj - 2;
-				for (int ii = jj - 1; ii >= lo; ii--) F[(size_t)ii * LW + lane] = LU_UPD(F[(size_t)ii * LW + lane], bj, ABW(ii, jj));
-			}
-		}
+		// mass flux, its divergence (:4092-4140), upwinding (:4153-4181): tracer_rhs_level; the diagonal matrix 1/dt: dgbtrs leaves b_j / (1/dt)
 		for (int k = 0; k < L; k++) {
+			const double f = tracer_rhs_level(p.ops, L, k, je, jn, ks != 0.0, ks,
+				[&](int l) { return qn[(size_t)l * LW + lane]; }, [&](int l) { return mixr[(size_t)l * LW + lane]; }, xd, xd, [&](int m) { return rhoe[(size_t)m * LW + lane]; });
 			const size_t so = (size_t)TMX_SLAB_Q(L, c, k) * NS;
-			const double val = xbase[so + col] - F[(size_t)k * LW + lane];
-			xup[so + col] = val;
-#pragma unroll
-			for (int t = 0; t < 3; t++) if (dep[t] >= 0) xup[so + dep[t]] = val;
+			xup[so + col] = xup[so + col] - tracer_explicit_solve(f, idt);
 		}
 	}
-	if (singular) atomicOr(flag, TMX_FLAG_SINGULAR);
-#undef ABW
 }
 
-// The same column update (implicit mode) with the level-parallel parts spread over NR row lanes per column: a workgroup =
-// 16 columns x NR row lanes.  Row lane t of a column evaluates xi_dot, the matrix rows, the tracer loads, the
-// right-hand side and the result stores of the levels k = t, t + NR, ...; every matrix entry and every right-hand-side entry is
-// formed by the lane that owns its row, in the order the sequential loops of k_vi_tracers accumulate it (flux terms, upwinding
-// of interface k then k + 1, 1/dt; velocity correction of interface k then k + 1), so the results are bit-identical; only the
-// factorisation and the two substitutions stay on one lane per column (pivot row / running entries in registers, the
-// next row prefetched from LDS).  LDS: (9L + 3) x 16 doubles per workgroup, so that at L = 30 five workgroups share a CU.
-template <int NR, int LWB> __global__ __launch_bounds__(NR << LWB) void k_vi_tracers_rows(KParams p, int nt, const double * __restrict__ xin, const double * __restrict__ w0,
-	const double * xbase, double * xup, double dt, int nunique, const int * __restrict__ ucol, const int * __restrict__ udep, int * __restrict__ flag)
-{
-	constexpr int LW = 1 << LWB;        // columns per workgroup (16 or 8)
-	extern __shared__ double smt[];
-	const int L = p.L, lane = threadIdx.x & (LW - 1), t = threadIdx.x >> LWB;
-	const size_t NS = (size_t)p.NS;
-	double * A = smt;                                // [L][4][LW]
-	double * F = A + (size_t)L * 4 * LW;             // [L][LW]
-	double * xd0 = F + (size_t)L * LW;               // [L+1][LW]
-	double * xd1 = xd0 + (size_t)(L + 1) * LW;       // [L+1][LW]
-	double * qn = xd1 + (size_t)(L + 1) * LW;        // [L][LW]
-	double * jmp = qn + (size_t)L * LW;              // [L+1][LW] upwind sign x metric x (W updated - W initial) per interface
-	const int uraw = blockIdx.x * LW + lane;
-	const bool valid = uraw < nunique;
-	const int u = valid ? uraw : nunique - 1;        // lanes of a ragged last workgroup redo the last column (no stores): barriers below
-	const int col = ucol ? ucol[u] : u;
-	const MetCol mc = met_col(p, col);
-	const double jn = p.g2d[G2_JN * NS + col], je = p.g2d[G2_JE * NS + col];
-	// row k of the band matrix in slots 0..2 (sub-, main, super-diagonal); after the factorisation: slot 0 of row j + 1 = the
-	// multiplier of step j, slots 1..3 of row j = row j of U (diagonal and the two entries right of it)
-#define AR(k_, s_) A[((size_t)(k_) * 4 + (s_)) * LW + lane]
-	// xi_dot on interfaces, initial and with the updated W (:3943-3957, :4059-4086)
-	for (int k = t; k <= L; k += NR) {
-		double x0v = 0.0, x1v = 0.0, jv = 0.0;
-		if (k >= 1 && k <= L - 1) {
-			const double ue = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_U(L, k + off) * NS + col]; });
-			const double ve = edge_sum(p.ops, L, TMX_OP_INTERP_NODE_TO_REDGE, k, [&](int off) { return xin[(size_t)TMX_SLAB_V(L, k + off) * NS + col]; });
-			double e0, e1, e2;
-			metric_edge(p, mc, k, col, e0, e1, e2);
-			const double wi = w0[(size_t)k * NS + col], wu = xup[(size_t)TMX_SLAB_W(L, k) * NS + col];
-			x0v = e0 * ue + e1 * ve + e2 * wi;
-			x1v = e0 * ue + e1 * ve + e2 * wu;
-			const double sw = (x0v > 0.0) ? 1.0 * e2 : ((x0v < 0.0) ? -1.0 * e2 : 0.0);
-			jv = sw * (wu - wi);
-		}
-		xd0[(size_t)k * LW + lane] = x0v; xd1[(size_t)k * LW + lane] = x1v; jmp[(size_t)k * LW + lane] = jv;
-	}
-	__syncthreads();
-	// matrix rows (:3959-4016), each entry by the owner of its row
-	for (int k = t; k < L; k += NR) {
-#pragma unroll
-		for (int d = -1; d <= 1; d++) {
-			const int n = k + d;
-			if (n < 0 || n >= L) { AR(k, d + 1) = 0.0; continue; }
-			double a = 0.0;
-			// d F_k / d q_n: DiffREdgeToNode x J_e / J_n x InterpNodeToREdge x xi_dot; interface m = k + mo, node n = m + no
-#pragma unroll
-			for (int mo = 0; mo <= 1; mo++) {
-				const int m = k + mo, no = n - m;
-				if (no < -2 || no > 1) continue;
-				a += OPC(TMX_OP_DIFF_REDGE_TO_NODE, k, mo) * je / jn * OPC(TMX_OP_INTERP_NODE_TO_REDGE, m, no) * xd0[(size_t)m * LW + lane];
-			}
-			// upwinding: interface a = k (this row as "a"), then a = k + 1 (this row as "a - 1")
-			if (k >= 1 && k <= L - 1) {
-				const double wgt = fabs(xd0[(size_t)k * LW + lane]);
-				if (d == -1) a -= wgt * OPC(TMX_OP_PENALTY_RIGHT, k, -1);
-				if (d == 0) a -= wgt * OPC(TMX_OP_PENALTY_RIGHT, k, 0);
-			}
-			if (k + 1 <= L - 1) {
-				const double wgt = fabs(xd0[(size_t)(k + 1) * LW + lane]);
-				if (d == 0) a -= wgt * OPC(TMX_OP_PENALTY_LEFT, k, 0);
-				if (d == 1) a -= wgt * OPC(TMX_OP_PENALTY_LEFT, k, 1);
-			}
-			if (d == 0) a += 1.0 / dt;
-			AR(k, d + 1) = a;
-		}
-	}
-	__syncthreads();
-	// dgbtf2 (kl = ku = 1, kv = 2), one lane per column, with the pivot candidate row carried in registers: at step j the
-	// candidate has entries (c0, c1) in columns j, j + 1 (the fill-in column j + 2 holds the zero dgbtf2 stores there); row j + 1
-	// is (l, d, u) in columns j .. j + 2.  Interchange when |l| > |c0| (idamax keeps the first of equals), multiplier = the other
-	// row's leading entry x (1 / pivot) (dscal), rank-1 update fused as in LU_UPD, skipped for a zero in the pivot row (dger).
-	bool singular = false;
-	unsigned long long jpmask = 0, jpmask_hi = 0, zeromask = 0, zeromask_hi = 0;
-	if (t == 0) {
-		double c0 = AR(0, 1), c1 = AR(0, 2);
-		double nl = (L > 1) ? AR(1, 0) : 0.0, nd = (L > 1) ? AR(1, 1) : 0.0, nu = (L > 1) ? AR(1, 2) : 0.0;
-		for (int jj = 0; jj < L - 1; jj++) {
-			const double l = nl, d = nd, un = nu;
-			if (jj + 2 < L) { nl = AR(jj + 2, 0); nd = AR(jj + 2, 1); nu = AR(jj + 2, 2); }
-			const bool jp = fabs(l) > fabs(c0);
-			const double piv = jp ? l : c0;
-			if (piv != 0.0) {
-				const double p1 = jp ? d : c1, p2 = jp ? un : 0.0;          // pivot row right of the diagonal
-				const double o0 = jp ? c0 : l, o1 = jp ? c1 : d, o2 = jp ? 0.0 : un;
-				if (jp) { jpmask |= 1ull << (jj & 63); if (jj >= 64) jpmask_hi |= 1ull << (jj - 64); }
-				const double r = 1.0 / piv;
-				const double m = o0 * r;
-				AR(jj, 1) = piv; AR(jj, 2) = p1; AR(jj, 3) = p2; AR(jj + 1, 0) = m;
-				c0 = (p1 != 0.0) ? LU_UPD(o1, m, p1) : o1;
-				c1 = (jp && p2 != 0.0) ? LU_UPD(o2, m, p2) : o2;
-			} else {
-				singular = true; zeromask |= 1ull << (jj & 63); if (jj >= 64) zeromask_hi |= 1ull << (jj - 64);
-				AR(jj, 1) = c0; AR(jj, 2) = c1; AR(jj, 3) = 0.0;       // l == c0 == 0: nothing eliminated, row j + 1 becomes the candidate
-				c0 = d; c1 = un;
-			}
-		}
-		AR(L - 1, 1) = c0; AR(L - 1, 2) = 0.0; AR(L - 1, 3) = 0.0;
-		if (c0 == 0.0) { singular = true; zeromask |= 1ull << ((L - 1) & 63); if (L - 1 >= 64) zeromask_hi |= 1ull << (L - 1 - 64); }
-	}
-	int dep[3];
-#pragma unroll
-	for (int q = 0; q < 3; q++) dep[q] = udep ? udep[u * 3 + q] : -1;
-	for (int c = 0; c < nt; c++) {
-		__syncthreads();        // the previous tracer's stores have read F
-		for (int k = t; k < L; k += NR) qn[(size_t)k * LW + lane] = xin[(size_t)TMX_SLAB_Q(L, c, k) * NS + col];
-		__syncthreads();
-		for (int k = t; k < L; k += NR) {
-			// mass flux with the updated xi_dot, its divergence (:4092-4140), upwinding with the initial xi_dot (:4153-4181): tracer_rhs_level
-			auto qcol = [&](int l) { return qn[(size_t)l * LW + lane]; };
-			double f = tracer_rhs_level(p.ops, L, k, je, jn, false, 0.0, qcol, qcol,
-				[&](int m) { return xd1[(size_t)m * LW + lane]; }, [&](int m) { return xd0[(size_t)m * LW + lane]; }, [](int) { return 0.0; });
-			// implicit velocity correction (:4183-4233): interface a = k (this row as "a"), then a = k + 1 (as "a - 1")
-#pragma unroll
-			for (int s_ = 0; s_ <= 1; s_++) {
-				const int a = k + s_;
-				if (a < 1 || a > L - 1) continue;
-				const double jump = jmp[(size_t)a * LW + lane];
-				if (s_ == 0) {
-					f -= OPC(TMX_OP_PENALTY_RIGHT, a, -1) * qn[(size_t)(a - 1) * LW + lane] * jump;
-					f -= OPC(TMX_OP_PENALTY_RIGHT, a, 0) * qn[(size_t)a * LW + lane] * jump;
-				} else {
-					f -= OPC(TMX_OP_PENALTY_LEFT, a - 1, 0) * qn[(size_t)(a - 1) * LW + lane] * jump;
-					f -= OPC(TMX_OP_PENALTY_LEFT, a - 1, 1) * qn[(size_t)a * LW + lane] * jump;
-				}
-			}
-			F[(size_t)k * LW + lane] = f;
-		}
-		__syncthreads();
-		if (t == 0) {
-			// dgbtrs: forward substitution with the stored multipliers and interchanges, the running entry in a register ...
-			double fc = F[lane], fn = (L > 1) ? F[(size_t)LW + lane] : 0.0, mm = (L > 1) ? AR(1, 0) : 0.0;
-			for (int jj = 0; jj < L - 1; jj++) {
-				const double f1 = fn, m = mm;
-				if (jj + 2 < L) { fn = F[(size_t)(jj + 2) * LW + lane]; mm = AR(jj + 2, 0); }
-				const unsigned long long bit = 1ull << (jj & 63);
-				const bool isz = (jj < 64) ? (zeromask & bit) != 0 : (zeromask_hi & (1ull << (jj - 64))) != 0;
-				const bool jp = (jj < 64) ? (jpmask & bit) != 0 : (jpmask_hi & (1ull << (jj - 64))) != 0;
-				const double top = (jp && !isz) ? f1 : fc, bot = (jp && !isz) ? fc : f1;
-				F[(size_t)jj * LW + lane] = top;
-				fc = isz ? bot : LU_UPD(bot, top, m);
-			}
-			// ... then dtbsv (upper, no transpose, non-unit), column oriented: entry j is divided by the diagonal and then leaves
-			// entries j - 1 and j - 2; entry i therefore receives column i + 2 before column i + 1.  b1 = entry j - 1 so far.
-			double cur = fc, b1 = (L > 1) ? F[(size_t)(L - 2) * LW + lane] : 0.0;
-			double dg = AR(L - 1, 1), u1 = (L > 1) ? AR(L - 2, 2) : 0.0, u2 = (L > 2) ? AR(L - 3, 3) : 0.0, fr = (L > 2) ? F[(size_t)(L - 3) * LW + lane] : 0.0;
-			for (int jj = L - 1; jj >= 0; jj--) {
-				const double dgj = dg, u1j = u1, u2j = u2, b2 = fr;
-				if (jj >= 1) dg = AR(jj - 1, 1);
-				if (jj >= 2) u1 = AR(jj - 2, 2);
-				if (jj >= 3) { u2 = AR(jj - 3, 3); fr = F[(size_t)(jj - 3) * LW + lane]; }
-				const bool nz = cur != 0.0;
-				const double x = nz ? cur / dgj : cur;
-				F[(size_t)jj * LW + lane] = x;
-				cur = nz ? LU_UPD(b1, x, u1j) : b1;
-				b1 = nz ? LU_UPD(b2, x, u2j) : b2;
-			}
-		}
-		__syncthreads();
-		if (valid)
-			for (int k = t; k < L; k += NR) {
-				const size_t so = (size_t)TMX_SLAB_Q(L, c, k) * NS;
-				const double val = xbase[so + col] - F[(size_t)k * LW + lane];
-				xup[so + col] = val;
-#pragma unroll
-				for (int q = 0; q < 3; q++) if (dep[q] >= 0) xup[so + dep[q]] = val;
-			}
-	}
-	if (singular && valid) atomicOr(flag, TMX_FLAG_SINGULAR);
-#undef AR
-}
+// LDS working set of k_v_tracers_explicit_column per workgroup of lw columns: xd0 and rhoe on the interfaces [L + 1] each, qn and mixr on
+// the levels [L] each: (4L + 2) x lw doubles
+static size_t vt_explicit_column_lds(int L, int lw) { return ((size_t)(L + 1) * 2 + (size_t)L * 2) * lw * sizeof(double); }
 
-// LDS working set of the column kernels per workgroup of lw columns: band matrix [L][4], right-hand side and tracer column [L] each,
-// nedge arrays on the interfaces [L + 1] (xi_dot initial / updated: (8L + 2) x lw doubles; k_vi_tracers_rows: the velocity jump too, (9L + 3) x lw)
-static size_t vt_lds(int L, int lw, int nedge) { return ((size_t)L * 4 + (size_t)L * 2 + (size_t)(L + 1) * nedge) * lw * sizeof(double); }
-
-// The columns a launch updates: all of them (ucol == nullptr), or the unique ones with up to three dependents each that receive a copy
-struct ColumnSet { int ncols; const int * ucol, * udep; };
-
-// row lanes per column of k_vi_tracers_rows: 16 (four wavefronts per 16 columns) up to 48 levels, 32 above; TMX_VT_NR = 4 | 8 | 16 | 32;
-// 8 columns per workgroup up to 48 levels (half the LDS per workgroup, twice the workgroups per CU), 16 above; TMX_VT_LW8 = 0 | 1
-static void launch_vt_rows(tmx_engine * e, const KParams & p, const ColumnSet & cs, const double * xin, const double * w0, const double * xbase, double * xup, double dt) {
-	const int nr_env = e->opt_vt_nr, lw8_env = e->opt_vt_lw8;      // options "vt_row_lanes", "vt_lw8"
-	const bool lw8 = lw8_env >= 0 ? lw8_env == 1 : p.L <= 48;    // ne30, 2 tracers: L30 1.308 (8 columns) / 1.358 (16) ms per step, L60 3.35 / 3.21
-	const int nr = nr_env ? nr_env : (p.L > 48 ? 32 : 16);       // measured at ne30: L30 1.36 (16) / 1.49 (32) ms, L60 3.50 (16) / 3.25 (32) ms per step
-#define LAUNCH_VTR(NR_, LWB_) do { \
-		const size_t lds_ = vt_lds(p.L, 1 << LWB_, 3); \
-		(void)hipFuncSetAttribute((const void *)k_vi_tracers_rows<NR_, LWB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-		hipLaunchKernelGGL((k_vi_tracers_rows<NR_, LWB_>), dim3((cs.ncols + (1 << LWB_) - 1) >> LWB_), dim3(NR_ << LWB_), lds_, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \
-			cs.ncols, cs.ucol, cs.udep, e->d_flag); } while (0)
-	if (lw8) { if (nr == 8) LAUNCH_VTR(8, 3); else if (nr == 32) LAUNCH_VTR(32, 3); else LAUNCH_VTR(16, 3); }
-	else if (nr == 4) LAUNCH_VTR(4, 4); else if (nr == 8) LAUNCH_VTR(8, 4); else if (nr == 32) LAUNCH_VTR(32, 4); else LAUNCH_VTR(16, 4);
-#undef LAUNCH_VTR
-}
-
-// The column update of the tracers on a set of columns by the LDS kernels.  Implicit mode (expl = false): k_vi_tracers_rows (option
-// "vt_rows", the default, where its 16-column working set fits a CU), else k_vi_tracers; explicit mode (ks, xref: uniform diffusion):
-// k_vi_tracers.  k_vi_tracers takes the most lanes (64 or 32) whose working set fits one CU; `lanes` = 32 | 16 | 8 asks for fewer.
-// Fewer columns per workgroup = more workgroups per CU: the kernel lives in LDS (dependent read-modify-write chains of ~100 cycles
-// each) and one 64-column workgroup fills a CU's LDS, i.e. ONE wavefront per CU.  With 16 columns per workgroup five wavefronts
-// share a CU and hide each other's LDS latency.  Returns -1 where no shape fits.
-static int launch_vt_columns(tmx_engine * e, const KParams & p, const ColumnSet & cs, const double * xin, const double * w0, const double * xbase, double * xup,
-	double dt, bool expl, double ks, const double * xref, int lanes)
-{
-	if (!expl && e->opt_vt_rows && vt_lds(p.L, 16, 3) <= 160 * 1024) { launch_vt_rows(e, p, cs, xin, w0, xbase, xup, dt); return 0; }
-	int lw = 0;
-	for (int l = 64; l >= 32 && !lw; l >>= 1) if (vt_lds(p.L, l, 2) <= 160 * 1024) lw = l;
-	if (!lw) return -1;
-	if (lanes < lw && (lanes == 32 || lanes == 16 || lanes == 8)) lw = lanes;
-	const size_t lds = vt_lds(p.L, lw, 2);
-#define LAUNCH_VT(LW_) do { (void)hipFuncSetAttribute((const void *)k_vi_tracers<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-	hipLaunchKernelGGL(k_vi_tracers<LW_>, dim3((cs.ncols + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \
-		cs.ncols, cs.ucol, cs.udep, e->d_flag, expl ? 1 : 0, ks, xref); } while (0)
-	if (lw == 64) LAUNCH_VT(64); else if (lw == 32) LAUNCH_VT(32); else if (lw == 16) LAUNCH_VT(16); else LAUNCH_VT(8);
-#undef LAUNCH_VT
+// 64 columns per workgroup, or 32 where only they fit the 160 KB of a CU; returns -1 where neither does
+static int launch_vt_explicit_column(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) {
+	const int lw = (vt_explicit_column_lds(p.L, 64) <= 160 * 1024) ? 64 : 32;
+	const size_t lds = vt_explicit_column_lds(p.L, lw);
+	if (lds > 160 * 1024) return -1;
+	const double ks = e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0;
+#define LAUNCH_VTC(LW_) do { (void)hipFuncSetAttribute((const void *)k_v_tracers_explicit_column<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+	hipLaunchKernelGGL(k_v_tracers_explicit_column<LW_>, dim3((p.ncol + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, xup, dt, ks, (const double *)e->d_ref); } while (0)
+	if (lw == 64) LAUNCH_VTC(64); else LAUNCH_VTC(32);
+#undef LAUNCH_VTC
 	return 0;
-}
-
-// UpdateColumnTracers behind the implicit column solve: the unique columns, their dependents written along (option "vt_lanes", default 16)
-int tmxk_vi_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * w0, const double * xbase, double * xup, double dt) {
-	if (e->nunique == 0 || e->nt == 0) return 0;
-	return launch_vt_columns(e, p, ColumnSet{ e->nunique, (const int *)e->d_ucol, (const int *)e->d_udep }, xin, w0, xbase, xup, dt, false, 0.0, nullptr, e->opt_vt_lanes);
 }
 
 #if TMX_EXP      // the form without LDS staging (option "vt_explicit_v1"), superseded by k_v_tracers_explicit_tile: experiments flavour only
 // UpdateColumnTracers in the fully explicit vertical mode, level-parallel.  There the matrix is the diagonal 1/dt, so the
 // update of (column, level, tracer) only needs the column within two levels: one thread per (column, level) evaluates
-// the right-hand side of k_vi_tracers' explicit branch (tracer_rhs_level, tmx_device.h) instead of one
+// the right-hand side of k_v_tracers_explicit_column (tracer_rhs_level, tmx_device.h) instead of one
 // lane walking the whole column out of LDS -- that form took 3.4 ms per launch at ne30 L40 (32 columns per workgroup, 82 KB
 // of LDS each), 75 % of a supercell step.
 __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, const double * __restrict__ xin, double * xup, double dt,
@@ -634,7 +294,7 @@ __global__ __launch_bounds__(256) void k_v_tracers_explicit(KParams p, int nt, c
 // The same update (k_v_tracers_explicit, experiments flavour: one thread per (column, level) with every operand from memory) with the shared operands of a tile staged once in LDS: a workgroup = 64 columns x 8 levels; xi_dot (and, with
 // uniform diffusion, rho) on the tile's 9 interfaces, rho on its 12 levels and per tracer the 12 column values and mixing-ratio
 // deviations (two fp64 divisions each) are evaluated by one thread each instead of by every thread whose stencil reaches them
-// (5 x for the divisions: 372 -> 264 us per launch at ne30 L40 with three tracers).  The right-hand side itself is tracer_rhs_level (tmx_device.h), as in k_vi_tracers.
+// (5 x for the divisions: 372 -> 264 us per launch at ne30 L40 with three tracers).  The right-hand side itself is tracer_rhs_level (tmx_device.h), as in k_v_tracers_explicit_column.
 __global__ __launch_bounds__(512) void k_v_tracers_explicit_tile(KParams p, int nt, const double * __restrict__ xin, double * xup, double dt,
 	double ks, const double * __restrict__ xref, int ntile, int xmode)
 {
@@ -965,15 +625,7 @@ int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * x
 		}
 		return 0;
 	}
-	return launch_vt_columns(e, p, ColumnSet{ p.ncol, nullptr, nullptr }, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, xup, xup, dt,
-		true, e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0, (const double *)e->d_ref, 64);
-}
-
-// UpdateColumnTracers at the end of StepImplicitTermsExplicitly (VerticalDynamicsFEM.cpp:600-608): the implicit column update
-// of the tracers, on every stored column (the reference loops over all nodes there, :541-542), in place on the update instance
-int tmxk_vi_tracers_all(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) {
-	if (e->nt == 0 || p.ncol == 0) return 0;
-	return launch_vt_columns(e, p, ColumnSet{ p.ncol, nullptr, nullptr }, xin, xin + (size_t)TMX_SLAB_W(p.L, 0) * p.NS, xup, xup, dt, false, 0.0, nullptr, 64);
+	return launch_vt_explicit_column(e, p, xin, xup, dt);
 }
 
 __global__ __launch_bounds__(256) void k_v_filter_tracers(KParams p, int nt, const double * __restrict__ area, double * x) {
@@ -1002,11 +654,251 @@ void tmxk_v_filter_tracers(tmx_engine * e, const KParams & p, double * x) {
 	hipLaunchKernelGGL(k_v_filter_tracers, dim3((p.ncol + 255) / 256, e->nt), dim3(256), 0, e->stream, p, e->nt, (const double *)e->d_area, x);
 }
 
-// Column physics: HeldSuarezPhysics::Perform (src/atm/HeldSuarezPhysics.cpp:60-301), Lorenz staggering.  Pointwise
-// in (column, level): backward-Euler boundary-layer friction on U,V (sigma from PressureFromRhoTheta(rho * rhotheta),
-// :107-126, as the reference writes it) and relaxation of rho*theta towards the equilibrium temperature with the
-// "Ullrich update" (:186-247).  The surface pressure is PressureFromRhoTheta(rho_e0 * rhotheta_e0) of the tracked surface
-// slots (`surf` = [2][NS]: what the reference finds in the interface entries of rho and rho*theta, :113-116), or, when the
-// caller pinned it, the input of tmx_set_patch_physics_inputs.
+// ---------------------------------------------------------------------------------------------
+// VerticalDynamicsFEM::StepImplicitTermsExplicitly (src/atm/VerticalDynamicsFEM.cpp:439-612):
+// update -= dt * F(initial) for rho*theta, W, rho on EVERY column (F = BuildF of the initial column).
 
-}      // namespace lu_fma / lu_nofma
+// UD (fully explicit mode with uniform diffusion): F additionally holds the vertical diffusion of rho*theta and W
+// relative to the reference column xref (cs = K_s / ztop^2, cw = K_v / ztop^2).
+// UVX: the thread of (column, level k < L) also applies V.StepExplicit's update of U,V (v_explicit_point: penalty and, with UD,
+// the vertical diffusion), which reads the same U,V,W columns and metric rows -- one launch less per stage and the operands
+// found in the cache
+template <bool UD, bool UVX>
+// KT_VC levels per workgroup.  A thread reads the levels k-2 .. k+2 of its column, so the level tiles of a column overlap by
+// four levels and every value is fetched 2.7 times over at the L2's memory side (PMC, ne30 L40: 514 MB of reads per launch for
+// 190 MB of operands: the level-neighbour tiles are 1 350 workgroups apart in dispatch order, on another XCD's L2).  Taller
+// tiles make the neighbours wavefronts of one workgroup, and lose: config 4's step takes 5.12 / 5.21 / 5.34 ms with 4 / 8 / 16
+// levels per workgroup (1 024-thread workgroups leave one per CU).  4 stays.
+#ifndef KT_VC
+#define KT_VC 4
+#endif
+__global__ __launch_bounds__(64 * KT_VC) void k_vi_terms_explicit(KParams p, const double * __restrict__ xin,
+	double * __restrict__ xup, double dt, const double * __restrict__ xref, double cs, double cw, int ntile, int xmode)
+{
+	const int L = p.L;
+	const size_t NS = (size_t)p.NS;
+	int bx, by;
+	if (!xcd_column_tile(xmode, ntile, (L + 1 + KT_VC - 1) / KT_VC, bx, by)) return;
+	const int col = (p.quads ? p.quads[bx] : bx) * 64 + threadIdx.x;
+	const int k = by * KT_VC + WAVE_UNIFORM(threadIdx.y);
+	if (col >= p.ncol || k > L) return;
+	ColConst cc;
+	cc.c2a0 = p.g2d[G2_C2A0 * NS + col]; cc.c2a1 = p.g2d[G2_C2A1 * NS + col]; cc.c2b1 = p.g2d[G2_C2B1 * NS + col];
+	cc.jn = p.g2d[G2_JN * NS + col]; cc.je = p.g2d[G2_JE * NS + col]; cc.drx = p.g2d[G2_DRX * NS + col];
+	cc.invdt = 1.0 / dt; cc.upc = 0.5 * (1.0 / (double)L); cc.cv = p.cp - p.Rd;
+	const MetCol mcol = met_col(p, col);
+	// the values to update, loaded with the operands (at the point of use their latency would follow the whole evaluation)
+	const double upW = xup[TMX_SLAB_W(L, k) * NS + col];
+	const double upT = (k < L) ? xup[TMX_SLAB_T(L, k) * NS + col] : 0.0, upR = (k < L) ? xup[TMX_SLAB_R(L, k) * NS + col] : 0.0;
+	const NodeLev nA = load_node(p, mcol, xin, k - 1, col), nB = load_node(p, mcol, xin, k, col), nC = load_node(p, mcol, xin, k + 1, col);
+	const EdgeLev eA = load_edge(p, mcol, xin, k - 1, col), eB = load_edge(p, mcol, xin, k, col), eC = load_edge(p, mcol, xin, k + 1, col);
+	double rP[TMX_BW], rW[TMX_BW], rR[TMX_BW], fP, fW, fR;
+	BlkCarry cy;
+	double udP = 0.0, udW = 0.0;
+	if (UD) {
+		// PrepareColumn :2104-2160: DiffDiff of the column minus DiffDiff of the reference column; W not on the boundaries
+		if (k < L) {
+			double dd = 0.0, ddr = 0.0;
+#pragma unroll
+			for (int off = -2; off <= 2; off++) {
+				const int l = k + off;
+				if (l < 0 || l >= L) continue;
+				const double c = OPC(TMX_OP_DIFFDIFF_NODE_TO_NODE, k, off);
+				dd += c * xin[(size_t)TMX_SLAB_T(L, l) * NS + col];
+				ddr += c * xref[(size_t)TMX_SLAB_T(L, l) * NS + col];
+			}
+			udP = cs * (dd - ddr);
+		}
+		if (k > 0 && k < L) {
+			double dd = 0.0, ddr = 0.0;
+#pragma unroll
+			for (int off = -2; off <= 2; off++) {
+				const int l = k + off;
+				if (l < 0 || l > L) continue;
+				const double c = OPC(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, off);
+				dd += c * xin[(size_t)TMX_SLAB_W(L, l) * NS + col];
+				ddr += c * xref[(size_t)TMX_SLAB_W(L, l) * NS + col];
+			}
+			udW = cw * (dd - ddr);
+		}
+	}
+	compute_block<false, UD>(p, p.ops, cc, k, nA, nB, nC, eA, eB, eC, rP, rW, rR, fP, fW, fR, cy, udP, udW);
+	if (k < L) {
+		xup[TMX_SLAB_T(L, k) * NS + col] = upT - dt * fP;
+		xup[TMX_SLAB_R(L, k) * NS + col] = upR - dt * fR;
+	}
+	xup[TMX_SLAB_W(L, k) * NS + col] = upW - dt * fW;
+	if (UVX && k < L) v_explicit_point<UD>(p, xin, xup, dt, xref, cw, col, k);
+}
+
+// The same update by a thread that walks a column (or one of `nseg` segments of it) block row by block row, as the column solve's
+// assembly does: the three node levels and three interfaces a block row touches in a sliding register window, the quantities a
+// block row shares with the next carried over (compute_block<CARRY>: one evaluation of the Exner function per level instead of
+// two, every state value loaded once instead of three to five times), the next levels loaded two iterations ahead, operator
+// coefficients and the 1 - eta table in LDS.  The uniform-diffusion stencils take the state's five levels from the window (the
+// value that has just left it, the three in it, the one about to enter) and keep sliding windows of the reference's.  A segment that
+// does not start at the bottom evaluates the block row below it first, only to fill the carry.  Same statements on the same
+// operands as k_vi_terms_explicit: bit-identical (tested).
+template <bool UD, bool CLOSED>
+__global__ __launch_bounds__(128) void k_vi_terms_explicit_slide(KParams p, const double * __restrict__ xin,
+	double * __restrict__ xup, double dt, const double * __restrict__ xref, double cs, double cw, int ntile, int xmode, int nseg)
+{
+	extern __shared__ double opsl_mem[];
+	double * opsl = opsl_mem;
+	const int L = p.L;
+	constexpr int MM = CLOSED ? 1 : 2;
+	double * etal = opsl_mem + TMX_OP_COUNT * (L + 1) * TMX_OPW;
+	// the exp / log tables of the Exner function in LDS too: read from global memory each lookup is a vector-memory load behind an
+	// s_waitcnt vmcnt(0), i.e. two waits per block row for every level prefetch in flight (the column solve's assembly: the same)
+	double * rmtab = etal + 2 * L + 1;
+	walk_tables_to_lds<CLOSED>(p, opsl, etal);
+	tmx_rm_tables_to_lds(rmtab, threadIdx.y * 64 + threadIdx.x, 128);
+	__syncthreads();
+	const size_t NS = (size_t)p.NS;
+	int col, k0, k1;      // block rows k0 .. k1 - 1 of 0 .. L
+	if (!walk_segment(p, xmode, ntile, nseg, L + 1, col, k0, k1)) return;
+	ColConst cc;
+	cc.c2a0 = p.g2d[G2_C2A0 * NS + col]; cc.c2a1 = p.g2d[G2_C2A1 * NS + col]; cc.c2b1 = p.g2d[G2_C2B1 * NS + col];
+	cc.jn = p.g2d[G2_JN * NS + col]; cc.je = p.g2d[G2_JE * NS + col]; cc.drx = p.g2d[G2_DRX * NS + col];
+	cc.invdt = 1.0 / dt; cc.upc = 0.5 * (1.0 / (double)L); cc.cv = p.cp - p.Rd;
+	const MetCol mcol = met_col(p, col);
+	const int kw = (k0 > 0) ? k0 - 1 : 0;      // first block row evaluated (k0 - 1: for the carry only)
+	// The window: block row k reads U, V, rho*theta, rho of the levels k - 1, k, k + 1 and W of the interfaces k - 1, k, k + 1; with the
+	// carry, the metric terms of level k and of the interfaces k, k + 1 only.  Levels k + 2 and k + 3 are in flight as raw values
+	// (their metric terms are arithmetic on per-column factors and the LDS table: evaluated when a level becomes the window's top).
+	struct Raw { double un, vn, pn, rn, we; };
+	auto raw = [&](int l) {      // (out-of-range levels carry the values of the nearest one, as load_node / load_edge)
+		Raw r;
+		const int lc = l < 0 ? 0 : (l >= L ? L - 1 : l), le = l < 0 ? 0 : (l > L ? L : l);
+		r.un = xin[TMX_SLAB_U(L, lc) * NS + col]; r.vn = xin[TMX_SLAB_V(L, lc) * NS + col];
+		r.pn = xin[TMX_SLAB_T(L, lc) * NS + col]; r.rn = xin[TMX_SLAB_R(L, lc) * NS + col];
+		r.we = xin[TMX_SLAB_W(L, le) * NS + col];
+		return r;
+	};
+	auto node_of = [&](const Raw & r, int l) {
+		NodeLev n; n.un = r.un; n.vn = r.vn; n.pn = r.pn; n.rn = r.rn;
+		const int lc = l < 0 ? 0 : (l >= L ? L - 1 : l);
+		metric_node3<MM>(p, mcol, lc, col, n.ca2, n.cb2, n.cx2, etal);
+		return n;
+	};
+	auto edge_of = [&](const Raw & r, int l) {
+		EdgeLev e; e.we = r.we;
+		const int le = l < 0 ? 0 : (l > L ? L : l);
+		metric_edge<MM>(p, mcol, le, col, e.ce0, e.ce1, e.ce2, etal);
+		return e;
+	};
+	Raw rA = raw(kw - 1), rN = raw(kw + 2);
+	NodeLev nB = load_node<MM>(p, mcol, xin, kw, col, etal), nC = load_node<MM>(p, mcol, xin, kw + 1, col, etal);
+	EdgeLev eB = load_edge<MM>(p, mcol, xin, kw, col, etal), eC = load_edge<MM>(p, mcol, xin, kw + 1, col, etal);
+	double pm2 = 0.0, wm2 = 0.0;      // rho*theta of level k - 2, W of interface k - 2 (what has left the window)
+	double tr[5] = { 0, 0, 0, 0, 0 }, wr[5] = { 0, 0, 0, 0, 0 };      // reference rho*theta on the levels, W on the interfaces k - 2 .. k + 2
+	auto ref_T = [&](int l) { return (UD && l >= 0 && l < L) ? xref[(size_t)TMX_SLAB_T(L, l) * NS + col] : 0.0; };
+	auto ref_W = [&](int l) { return (UD && l >= 0 && l <= L) ? xref[(size_t)TMX_SLAB_W(L, l) * NS + col] : 0.0; };
+	if (UD) {
+		if (kw - 2 >= 0) { pm2 = xin[(size_t)TMX_SLAB_T(L, kw - 2) * NS + col]; wm2 = xin[(size_t)TMX_SLAB_W(L, kw - 2) * NS + col]; }
+#pragma unroll
+		for (int t = 0; t < 5; t++) { tr[t] = ref_T(kw - 2 + t); wr[t] = ref_W(kw - 2 + t); }
+	}
+	double upT = 0.0, upR = 0.0, upW = 0.0;
+	if (kw == k0) {
+		upW = xup[TMX_SLAB_W(L, kw) * NS + col];
+		if (kw < L) { upT = xup[TMX_SLAB_T(L, kw) * NS + col]; upR = xup[TMX_SLAB_R(L, kw) * NS + col]; }
+	}
+	BlkCarry cy = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+#pragma unroll 1
+	for (int k = kw; k < k1; k++) {
+		// two levels ahead: the level that enters the window after the next block row; the reference's entering values and the
+		// values the next block row updates
+		const Raw rNN = raw(k + 3);
+		const double trn = ref_T(k + 3), wrn = ref_W(k + 3);
+		double upTn = 0.0, upRn = 0.0, upWn = 0.0;
+		if (k + 1 < k1) {
+			upWn = xup[TMX_SLAB_W(L, k + 1) * NS + col];
+			if (k + 1 < L) { upTn = xup[TMX_SLAB_T(L, k + 1) * NS + col]; upRn = xup[TMX_SLAB_R(L, k + 1) * NS + col]; }
+		}
+		double udP = 0.0, udW = 0.0;
+		if (UD) {
+			const double tw[5] = { pm2, rA.pn, nB.pn, nC.pn, rN.pn }, ww[5] = { wm2, rA.we, eB.we, eC.we, rN.we };
+			if (k < L) {
+				double dd = 0.0, ddr = 0.0;
+#pragma unroll
+				for (int off = -2; off <= 2; off++) {
+					const int l = k + off;
+					if (l < 0 || l >= L) continue;
+					const double c = OPCL(TMX_OP_DIFFDIFF_NODE_TO_NODE, k, off);
+					dd += c * tw[off + 2];
+					ddr += c * tr[off + 2];
+				}
+				udP = cs * (dd - ddr);
+			}
+			if (k > 0 && k < L) {
+				double dd = 0.0, ddr = 0.0;
+#pragma unroll
+				for (int off = -2; off <= 2; off++) {
+					const int l = k + off;
+					if (l < 0 || l > L) continue;
+					const double c = OPCL(TMX_OP_DIFFDIFF_REDGE_TO_REDGE, k, off);
+					dd += c * ww[off + 2];
+					ddr += c * wr[off + 2];
+				}
+				udW = cw * (dd - ddr);
+			}
+		}
+		double rP[TMX_BW], rW[TMX_BW], rR[TMX_BW], fP, fW, fR;
+		{
+			NodeLev nA; nA.un = rA.un; nA.vn = rA.vn; nA.pn = rA.pn; nA.rn = rA.rn; nA.ca2 = 0.0; nA.cb2 = 0.0; nA.cx2 = 0.0;      // (with the carry a block row reads no metric term of level k - 1)
+			EdgeLev eA; eA.we = rA.we; eA.ce0 = 0.0; eA.ce1 = 0.0; eA.ce2 = 0.0;
+			compute_block<true, UD>(p, opsl, cc, k, nA, nB, nC, eA, eB, eC, rP, rW, rR, fP, fW, fR, cy, udP, udW, rmtab);
+		}
+		const double resT = upT - dt * fP, resR = upR - dt * fR, resW = upW - dt * fW;
+		pm2 = rA.pn; wm2 = rA.we;
+		rA.un = nB.un; rA.vn = nB.vn; rA.pn = nB.pn; rA.rn = nB.rn; rA.we = eB.we;
+		nB = nC; eB = eC;
+		nC = node_of(rN, k + 2); eC = edge_of(rN, k + 2);
+		rN = rNN;
+		tr[0] = tr[1]; tr[1] = tr[2]; tr[2] = tr[3]; tr[3] = tr[4]; tr[4] = trn;
+		wr[0] = wr[1]; wr[1] = wr[2]; wr[2] = wr[3]; wr[3] = wr[4]; wr[4] = wrn;
+		upT = upTn; upR = upRn; upW = upWn;
+		// The block row's stores LAST, behind the window's move (which evaluates the metric terms of the level that enters, i.e. reads values
+		// loaded an iteration ago): the stores sit in a branch, the compiler cannot count them, and a loaded value first used behind them waits
+		// for everything in flight -- the stores' own completion and the prefetch of two levels ahead -- once per block row.  The values the
+		// next block row updates are made to land before the stores too (they were loaded with this block row's operands).
+		asm volatile("" : "+v"(upT), "+v"(upR), "+v"(upW));
+		if (k >= k0) {
+			if (k < L) {
+				xup[TMX_SLAB_T(L, k) * NS + col] = resT;
+				xup[TMX_SLAB_R(L, k) * NS + col] = resR;
+			}
+			xup[TMX_SLAB_W(L, k) * NS + col] = resW;
+		}
+	}
+}
+
+void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv) {
+	const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
+	const size_t lds_slide = walk_lds_bytes(p.L, TMX_RMTAB_DOUBLES);
+	if (e->opt_vite_walk < 0 && !with_uv && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
+		const int nseg = walk_segments(e->opt_vite_walk, nt_, p.L + 1, 2048);
+		dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
+		const bool ud = e->udiff && e->fully_explicit;
+		const double z2 = e->cfg.ztop * e->cfg.ztop;
+		const double cs = ud ? e->cfg.uniform_diffusion_scalar / z2 : 0.0, cw = ud ? e->cfg.uniform_diffusion_vector / z2 : 0.0;
+#define LAUNCH_VS(UD_, CL_) hipLaunchKernelGGL((k_vi_terms_explicit_slide<UD_, CL_>), grd, blk, lds_slide, e->stream, p, xin, xup, dt, (const double *)(ud ? e->d_ref : nullptr), cs, cw, nt_, xm, nseg)
+		if (ud) { if (p.closed) LAUNCH_VS(true, true); else LAUNCH_VS(true, false); }
+		else { if (p.closed) LAUNCH_VS(false, true); else LAUNCH_VS(false, false); }
+#undef LAUNCH_VS
+		return;
+	}
+	dim3 blk(64, KT_VC), grd(xcd_column_grid(xm, nt_, (p.L + 1 + KT_VC - 1) / KT_VC));
+	if (e->udiff && e->fully_explicit) {
+		const double z2 = e->cfg.ztop * e->cfg.ztop;
+#if TMX_EXP      // (option "vx_fused", measured slower: experiments flavour only)
+		if (with_uv) hipLaunchKernelGGL((k_vi_terms_explicit<true, true>), grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)e->d_ref,
+			e->cfg.uniform_diffusion_scalar / z2, e->cfg.uniform_diffusion_vector / z2, nt_, xm);
+		else
+#endif
+		hipLaunchKernelGGL((k_vi_terms_explicit<true, false>), grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)e->d_ref,
+			e->cfg.uniform_diffusion_scalar / z2, e->cfg.uniform_diffusion_vector / z2, nt_, xm);
+	} else
+		hipLaunchKernelGGL((k_vi_terms_explicit<false, false>), grd, blk, 0, e->stream, p, xin, xup, dt, (const double *)nullptr, 0.0, 0.0, nt_, xm);
+}

@@ -1,5 +1,6 @@
-// tmx_lu_select.hip -- the launchers of the vertical operators, dispatched to one of the two compiled flavours of the band LU
-// (tmx_k_column.hip, tmx_k_vertical.hip: namespaces lu_fma / lu_nofma) by the engine's option "lu_fma".
+// tmx_lu_select.hip -- the launchers of the kernels that hold the band LU, dispatched to one of its two compiled flavours (tmx_k_column.hip,
+// tmx_k_tracer_solve.hip: namespaces lu_fma / lu_nofma) by the engine's option "lu_fma".  Only these differ between the flavours: the
+// column solve and the implicit column update of the tracers.  Every other vertical launcher is an ordinary function of tmx_k_vertical.hip.
 //
 // Why two: LAPACK builds dgbtf2 / dgbtrs / dtbsv from dger and friends, and whether the update a - l * u is ONE rounding (a fused
 // multiply-add: OpenBLAS, MKL on its AVX2 / AVX-512 code paths) or TWO (a netlib build without FMA contraction, MKL where it dispatches a
@@ -13,30 +14,22 @@
 #include <cstring>
 
 #define TMX_LU_LAUNCHERS(NS_) namespace NS_ { \
-	void tmxk_v_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_udiff_uv); \
 	void tmxk_vi_assemble(tmx_engine * e, const KParams & p, const double * xin, double dt); \
 	void tmxk_vi_solve(tmx_engine * e, const KParams & p, const double * xin, double * xup); \
 	void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt); \
-	void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv); \
 	int tmxk_vi_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * w0, const double * xbase, double * xup, double dt); \
-	void tmxk_v_filter_tracers(tmx_engine * e, const KParams & p, double * x); \
-	int tmxk_vi_tracers_all(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt); \
-	int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt); }
+	int tmxk_vi_tracers_all(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt); }
 TMX_LU_LAUNCHERS(lu_fma)
 TMX_LU_LAUNCHERS(lu_nofma)
 #define PICK(CALL_) (e->lu_fma ? lu_fma::CALL_ : lu_nofma::CALL_)
 
-void tmxk_v_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_udiff_uv) { PICK(tmxk_v_explicit(e, p, xin, xup, dt, with_udiff_uv)); }
 #if TMX_EXP      // the two-kernel cross-check path of the column solve: experiments flavour of the library only
 void tmxk_vi_assemble(tmx_engine * e, const KParams & p, const double * xin, double dt) { PICK(tmxk_vi_assemble(e, p, xin, dt)); }
 void tmxk_vi_solve(tmx_engine * e, const KParams & p, const double * xin, double * xup) { PICK(tmxk_vi_solve(e, p, xin, xup)); }
 #endif
 void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) { PICK(tmxk_vi_fused(e, p, xin, xup, dt)); }
-void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv) { PICK(tmxk_vi_terms_explicit(e, p, xin, xup, dt, with_uv)); }
 int tmxk_vi_tracers(tmx_engine * e, const KParams & p, const double * xin, const double * w0, const double * xbase, double * xup, double dt) { return PICK(tmxk_vi_tracers(e, p, xin, w0, xbase, xup, dt)); }
-void tmxk_v_filter_tracers(tmx_engine * e, const KParams & p, double * x) { PICK(tmxk_v_filter_tracers(e, p, x)); }
 int tmxk_vi_tracers_all(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) { return PICK(tmxk_vi_tracers_all(e, p, xin, xup, dt)); }
-int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) { return PICK(tmxk_vi_tracers_explicit(e, p, xin, xup, dt)); }
 
 // ---------------------------------------------------------------------------------------------
 // Which flavour does the CALLER'S LAPACK compute?  (LAPACK::DGBSV call site: src/base/LinearAlgebra.cpp:156-202.)

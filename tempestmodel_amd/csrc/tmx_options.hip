@@ -72,10 +72,10 @@ static const OptionDef g_options[] = {
 	{ "vt_explicit_walk", "TMX_VT_WALK", ANY_TIME, F(opt_vt_walk), ANY, BUT(1, INT_MAX), { AS_INT }, "explicit tracer update: -1000 (default) a sliding register window over column segments, their number chosen from the grid size; -n = n segments; 0 = the LDS-tiled level-parallel kernel; 4, 5, 6, 8, 10 = that many levels per thread held in registers (experiments build)" },
 	{ "vite_walk", "TMX_VITE_WALK", ANY_TIME, F(opt_vite_walk), ANY, ALL, { AS_INT }, "explicitly evaluated implicit terms (StepImplicitTermsExplicitly): -1000 (default) a sliding register window over column segments, their number chosen from the grid size; -n = n segments; 0 = the level-parallel kernel" },
 	{ "vx_walk", "TMX_VX_WALK", ANY_TIME, F(opt_vx_walk), ANY, ALL, { AS_INT }, "V.StepExplicit's U,V update: -1000 (default) a sliding register window over column segments, their number chosen from the grid size; -n = n segments; 0 = the level-parallel kernel" },
-	{ "vt_lanes", "TMX_VT_LANES", ANY_TIME, F(opt_vt_lanes), ONE_OF(8, 16, 32, 64), DEFAULT_ONLY, { AS_INT }, "A/B switch, experiments flavour only: columns per workgroup of the one-lane tracer column kernel (16)" },
+	{ "vt_lanes", "TMX_VT_LANES", ANY_TIME, F(opt_vt_lanes), ONE_OF(8, 16, 32, 64), DEFAULT_ONLY, { AS_INT }, "A/B switch, experiments flavour only: columns per workgroup of the implicit tracer kernel's one-row-lane form, \"vt_rows\" = 0 (16)" },
 	{ "vt_lw8", "TMX_VT_LW8", ANY_TIME, F(opt_vt_lw8), R(-1, 1), DEFAULT_ONLY, { AS_INT }, "A/B switch, experiments flavour only: row-parallel tracer kernel: 8 columns per workgroup (-1 auto)" },
 	{ "vt_row_lanes", "TMX_VT_NR", ANY_TIME, F(opt_vt_nr), ONE_OF(0, 4, 8, 16, 32), DEFAULT_ONLY, { AS_INT }, "A/B switch, experiments flavour only: row lanes of that kernel (0 auto)" },
-	{ "vt_rows", "TMX_VT_ROWS", ANY_TIME, F(opt_vt_rows), R(0, 1), ALL, { AS_INT }, "1 (default): row-parallel implicit tracer update" },
+	{ "vt_rows", "TMX_VT_ROWS", ANY_TIME, F(opt_vt_rows), R(0, 1), ALL, { AS_INT }, "1 (default): implicit tracer update with several row lanes per column; 0: the same kernel with one row lane per column, the serial order (cross-check)" },
 	{ "lu_fma", "TMX_LU_FMA", ANY_TIME, F(lu_fma), R(0, 1), ALL, { AS_INT }, "band LU of the column solves: 1 (default) updates a - l u as ONE rounding (fused multiply-add: a reference linked to OpenBLAS, or to MKL on its FMA code paths), 0 = multiply and subtract rounded separately (a BLAS without fused multiply-adds); tmx_lu_flavour_from_dgbsv asks the caller's own LAPACK" },
 	{ "h_walk_udiff", "TMX_H_WALK_UDIFF", ANY_TIME, F(opt_h_walk_udiff), R(0, 2), ALL, { AS_INT }, "uniform-diffusion configurations: the explicit stage's walk applies the horizontal uniform diffusion to its results in registers (1) and V.StepExplicit's U,V part behind it (2, default); 0 = k_uniform_diffusion and k_v_explicit as passes of their own (bit-identical)" },
 	{ "hv_walk", "TMX_HV_WALK", ANY_TIME, F(opt_hv_walk), R(-64, 1), ALL, { AS_INT }, "hyperviscosity pass on the node-unique layout: 1 (default) a wavefront walks a segment of levels (k_hv_walk; -n: n segments per column), 0 = the level-parallel k_hypervis (bit-identical)" },

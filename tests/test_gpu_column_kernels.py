@@ -43,8 +43,11 @@ def test_level_parallel_explicit_tracer_update_is_bit_identical_to_the_column_ke
 
 
 def test_row_parallel_implicit_tracer_update_is_bit_identical_to_the_column_kernel(monkeypatch):
-    """UpdateColumnTracers in the implicit mode: the kernel with four row lanes per column (default) and the one-lane-per-column
-    kernel (TMX_VT_ROWS=0) give identical doubles over whole ARS343 steps, and so does ARK232's all-columns form."""
+    """UpdateColumnTracers in the implicit mode: the kernel with several row lanes per column (default) and its one-row-lane form
+    (TMX_VT_ROWS=0: k_vi_tracers_rows<1, .>, the serial order) give identical doubles over whole ARS343 steps, and so does ARK232's
+    all-columns form.  Both are ONE kernel text, so this holds the row-lane decomposition -- who owns which row, the barriers, the pivot
+    row carried in registers -- to its own serial form, not to a second factorisation.  The separately written factorisation the suite
+    relies on is the oracle's orc_dgbsv, which the CPU tests pin against LAPACK and test_gpu_tracer_column_shapes.py compares both forms with."""
     from tempestmodel_amd.engine import Engine
     d = gu.load("steps_tracers_ne3_L6_p6.npz")
     g, _ = gu.make_grid(3, 6, 6, ntracers=2)

@@ -12,7 +12,7 @@ options the production library accepts, at the level counts where something chan
     L = 30      the headline's level count; two tracers
     L = 31      odd, production-sized
     L = 36, 37  the two sides of the automatic ring depth 3 -> 2 with two pairs per workgroup
-    L = 48, 49  the two sides of the implicit tracer column kernel's shape switch (launch_vt_rows); two tracers
+    L = 48, 49  the two sides of the implicit tracer column kernel's shape switch (launch_vt_solve, tmx_k_tracer_solve.hip); two tracers
     L = 60      config 5's level count; two tracers
 
 Oracle and device see identical inputs, so the bar is the project's own for that comparison: EXACT."""

@@ -30,7 +30,9 @@ from test_gpu_stage_walk_segments import _errs, _terrs, _finite
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(3, 4), (7, 4), (7, 1)]
-SHAPES_IMPLICIT = [(4, 4), (7, 4), (7, 1)]      # (see above)
+# (see above); 35 and 36 levels: the two sides of the one-row-lane kernel's switch from 64 to 32 columns per workgroup in the all-columns
+# form -- its working set, (9L + 3) doubles per column, fits the 160 KB of a CU 64 times up to L = 35
+SHAPES_IMPLICIT = [(4, 4), (7, 4), (7, 1), (35, 1), (36, 1)]
 DT = 0.7
 
 
@@ -117,8 +119,11 @@ def test_explicit_tracer_column_update_vs_oracle(L, nt, ud):
 @pytest.mark.parametrize("L,nt", SHAPES_IMPLICIT, ids=["L%d_nt%d" % s for s in SHAPES_IMPLICIT])
 def test_implicit_tracer_column_update_vs_oracle(L, nt):
     """Implicit vertical mode: the tracer columns behind the column solve of V.StepImplicit (unique columns, dependents written along) and
-    ARK232's all-columns form at the end of StepImplicitTermsExplicitly, by the row-lane kernel (vt_rows = 1, the default) and by the
-    one-lane kernel (0): state and tracers equal the oracle's."""
+    ARK232's all-columns form at the end of StepImplicitTermsExplicitly, by the row-lane kernel (vt_rows = 1, the default) and by its
+    one-row-lane form (0: k_vi_tracers_rows<1, .>, the serial order): state and tracers equal the oracle's.
+    The two are one kernel text: between them vt_rows = 0 cross-checks the row-lane decomposition (ownership of rows, barriers, the
+    register-carried pivot row) against its own serial form.  The separately written factorisation is on the other side of this
+    comparison: the oracle's orc_dgbsv, which the CPU tests pin against LAPACK."""
     from tempestmodel_amd.engine import Engine
     g, _, tr = _case(L, nt)
     calls = ("v_step_implicit", "v_step_implicit_terms_explicitly")
@@ -133,4 +138,45 @@ def test_implicit_tracer_column_update_vs_oracle(L, nt):
             e.close()
         assert max(_terrs(got[0][1], tr)) > 0.0 and max(_terrs(got[1][1], tr)) > 0.0, rows      # both updates changed the tracers
         _compare(bad, (L, nt, "vt_rows", rows), calls, got, want)
+    assert not bad, bad
+
+
+# (L, tracers) of the multiply + subtract case below.  At (7, 4) the oracle's two modes of the band LU leave different tracers behind
+# V.StepImplicit (checked on the CPU, where the oracle runs: 2.1e-17 of the tracers' maximum, state 3.4e-16; at (30, 4) 1.5e-16 and 8.3e-15),
+# so the smallest L of {7, 30} is taken.  Behind StepImplicitTermsExplicitly the two modes leave the SAME tracers and state at both level
+# counts (0.0): there W is not the column solve's, and with dt = 0.7 the tridiagonal matrix is so dominated by 1/dt that a - l u rounds
+# alike either way.  So what separates the modes in this case reaches the tracers through the W of the column solve as well.
+SHAPE_NOFMA = (7, 4)
+
+
+def test_implicit_tracer_column_update_with_the_multiply_subtract_band_lu():
+    """Option "lu_fma" = 0 (band-LU updates as multiply and subtract, rounded separately) in the tracers' column solve, by the row-lane
+    kernel and by its one-row-lane form: state and tracers equal the oracle's under orc_set_lu_fma(0), and behind V.StepImplicit the
+    oracle's two modes differ at this shape (SHAPE_NOFMA: what does and what does not separate them here)."""
+    from oracle_lib import lib
+    from tempestmodel_amd.engine import Engine
+    L, nt = SHAPE_NOFMA
+    g, _, tr = _case(L, nt)
+    calls = ("v_step_implicit", "v_step_implicit_terms_explicitly")
+    fused = _oracle_calls(L, nt, calls)
+    bad = []
+    try:
+        lib().orc_set_lu_fma(0)
+        want = _oracle_calls(L, nt, calls)
+        for name, (_, ft), (_, wt) in zip(calls, fused, want):
+            diff = max(_terrs(ft, wt))
+            print("oracle, fused against multiply + subtract:", name, diff)
+            assert diff < float("inf"), name
+            if name == "v_step_implicit":
+                assert EXACT < diff, name
+        for rows in (1, 0):
+            e = Engine(g, options={"vt_rows": rows, "lu_fma": 0})
+            try:
+                got = _device_calls(e, L, nt, calls)
+            finally:
+                e.close()
+            assert max(_terrs(got[0][1], tr)) > 0.0 and max(_terrs(got[1][1], tr)) > 0.0, rows
+            _compare(bad, (L, nt, "lu_fma", 0, "vt_rows", rows), calls, got, want)
+    finally:
+        lib().orc_set_lu_fma(1)
     assert not bad, bad
