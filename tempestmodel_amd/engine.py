@@ -166,6 +166,11 @@ def default_owner(npatch, n_ranks):
     return [p * n_ranks // npatch for p in range(npatch)]      # remainder spread over the ranks, none left empty
 
 
+def reference_owner(npatch, n_ranks):
+    """The reference's own map, round-robin (Grid::DistributePatches, Grid.cpp:1038-1062: m_vecPatchProcessor[n] = n % nSize): what the adapter hands over under MPI."""
+    return [p % n_ranks for p in range(npatch)]
+
+
 class Engine:
     """One engine per process / GPU, built from a :class:`tempestmodel_amd.cubed_sphere.CubedSphereGrid`
     (or anything exposing the same reference-layout arrays)."""

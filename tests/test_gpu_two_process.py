@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import owner_maps_common as om
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -25,11 +26,12 @@ def _free_port():
 NE, LEV, NPATCH = 12, 6, 24      # ne12 on 24 patches: the smallest layout on which every rank owns early AND late tiles (boundary-first stages on)
 
 
-def _run_ranks(world, scheme, ntr, steps, out, **extra_env):
+def _run_ranks(world, scheme, ntr, steps, out, grid=(NE, LEV, NPATCH), owner_map=None, **extra_env):
+    """grid: (ne, levels, patches) of the case; owner_map: a name of owner_maps_common.OWNER_MAPS, None: the engine's default (block) map."""
     port = _free_port()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
-    procs = [subprocess.Popen([sys.executable, WORKER, str(r), str(world), str(port), out, scheme, str(ntr), str(steps), str(NE), str(LEV), str(NPATCH)],
-                              env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(world)]
+    procs = [subprocess.Popen([sys.executable, WORKER, str(r), str(world), str(port), out, scheme, str(ntr), str(steps)] + [str(v) for v in grid]
+                              + ([owner_map] if owner_map else []), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(world)]
     logs = []
     for p in procs:
         try:
@@ -47,23 +49,36 @@ def _run_ranks(world, scheme, ntr, steps, out, **extra_env):
     # a time-out on rank 0 (it steps alone for one step), then tmx_halo_p2p_reset on every rank and the run proper
     (2, "recover-ars343", 0, {"TMX_P2P_TIMEOUT_S": "2"})])
 def test_ranks_in_separate_processes_match_one_engine(world, scheme, ntr, env):
+    _ranks_match_one_engine(world, scheme, ntr, env, (NE, LEV, NPATCH), None)
+
+
+@pytest.mark.parametrize("case", om.TWO_PROCESS_CASES, ids=om.case_id)
+def test_ranks_in_separate_processes_under_the_reference_map(case):
+    """The same through the peer-to-peer transport (k_pack_p2p) with the patches dealt round-robin, as Grid::DistributePatches deals them:
+    ne14 on 24 patches, where every rank has early and late tiles under that map (test_owner_maps_host.py)."""
+    assert case["map"] == "reference"
+    _ranks_match_one_engine(case["ranks"], case["scheme"], case["ntr"], {}, (case["ne"], case["L"], case["npatch"]), case["map"])
+
+
+def _ranks_match_one_engine(world, scheme, ntr, env, grid, owner_map):
     from tempestmodel_amd.engine import Engine
     steps = 3
-    g, st = gu.make_grid(NE, LEV, NPATCH, ntracers=ntr)
+    ne, lev, npatch = grid
+    g, st = gu.make_grid(ne, lev, npatch, ntracers=ntr)
     single = Engine(g)
     try:
         single.upload_state(0, st)
         if ntr:
             single.upload_tracers(0, [g.initial_tracers[P.index] for P in g.patches])
         for k in range(steps):
-            single.step(scheme.replace("recover-", ""), 200.0 * 4 / NE, first=(k == 0))
+            single.step(scheme.replace("recover-", ""), 200.0 * 4 / ne, first=(k == 0))
         single.sync()
         ref = single.download_state(0)
         reft = single.download_tracers(0) if ntr else None
     finally:
         single.close()
     with tempfile.TemporaryDirectory() as out:
-        _run_ranks(world, scheme, ntr, steps, out, **env)
+        _run_ranks(world, scheme, ntr, steps, out, grid=grid, owner_map=owner_map, **env)
         seen = set()
         for r in range(world):
             d = np.load(os.path.join(out, "rank%d.npz" % r))
@@ -75,7 +90,7 @@ def test_ranks_in_separate_processes_match_one_engine(world, scheme, ntr, env):
                 assert np.array_equal(d["e%d" % p][3, 1:-1, 1:-1], ref[p][1][3, 1:-1, 1:-1]), (r, p)
                 if ntr:
                     assert np.array_equal(d["t%d" % p][:, 1:-1, 1:-1], reft[p][:, 1:-1, 1:-1]), (r, p)
-        assert seen == set(range(24))
+        assert seen == set(range(npatch))
         if scheme.startswith("recover-"):
             msg = open(os.path.join(out, "rank0.txt")).read()
             assert "did not arrive" in msg, msg       # the lone step did fail, and said so

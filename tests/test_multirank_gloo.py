@@ -13,23 +13,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _col_lookup(grid, owner, rank, np_):
-    """column index -> (patch, i, j) for the local patches, same enumeration as the engine."""
-    cols = {}
-    base = 0
-    for P in grid.patches:
-        if owner[P.index] != rank:
-            continue
-        nea = (P.ga1 - P.ga0) // np_; neb = (P.gb1 - P.gb0) // np_
-        for a in range(nea):
-            for b in range(neb):
-                for ii in range(np_):
-                    for jj in range(np_):
-                        cols[(base + a * neb + b) * 16 + ii * 4 + jj] = (P.index, 1 + a * np_ + ii, 1 + b * np_ + jj)
-        base += nea * neb
-    return cols
-
-
 def _worker(rank, world, port, q):
     for p in (ROOT, HERE):
         if p not in sys.path:
@@ -40,6 +23,7 @@ def _worker(rank, world, port, q):
     import golden_util as gu
     from oracle_lib import Oracle
     from tempestmodel_amd.engine import Engine, default_owner
+    from owner_maps_common import column_lookup, execute_plan
     d = gu.load("steps_ne4_L6_p24.npz")
     g, _ = gu.make_grid(4, 6, 24)
     L = g.L
@@ -76,48 +60,16 @@ def _worker(rank, world, port, q):
     for peer, b in bufs.items():
         ghost[recv[:, 3] == peer] = b.numpy()
 
-    # group averaging exactly as k_dss does it
-    cols = _col_lookup(g, owner, rank, g.np)
-    got = [(n.copy(), ed.copy()) for (n, ed) in start]
+    # group averaging exactly as k_dss does it (owner_maps_common.execute_plan: shared with test_owner_maps_host.py)
+    tab = dict(NS=NS, send=send, recv=recv, grp=grp, gx=gx, gt=gt, M=M)
     worst = 0.0
-    for gi, row in enumerate(grp):
-        n = row[0]; mem = row[1:1 + n]
-        vals = []
-        for c in mem:
-            vals.append(column_values(*cols[c]) if c < NS else ghost[c - NS])
-        vals = np.array(vals)
-
-        ty = [(int(gt[gi]) >> (2 * m)) & 3 for m in range(4)]
-
-        def comb(v, m):
-            # k_dss / GridCSGLL::ApplyDSS order of operations (see tmx_host.hip, "device group tables")
-            if n == 2:
-                return 0.5 * (v[0] + v[1])
-            if n == 4:
-                pr = {0: ((0, 1), (2, 3)), 1: ((0, 2), (1, 3)), 2: ((0, 3), (1, 2))}[ty[m]]
-                return 0.5 * (0.5 * (v[pr[0][0]] + v[pr[0][1]]) + 0.5 * (v[pr[1][0]] + v[pr[1][1]]))
-            nx, pv = (m + 1) % 3, (m + 2) % 3
-            f, s2 = (pv, nx) if ty[m] else (nx, pv)
-            return (1.0 / 3.0) * ((v[m] + v[f]) + v[s2])
-        res = np.array([comb(vals, m) for m in range(n)])
-        if gx[gi] >= 0:
-            T = M[gx[gi]]
-            ua = vals[:, 0:L]; ub = vals[:, L:2 * L]
-            for m in range(n):
-                fa = np.array([ua[q] if q == m else T[m, q, 0, 0] * ua[q] + T[m, q, 0, 1] * ub[q] for q in range(n)])
-                fb = np.array([ub[q] if q == m else T[m, q, 1, 0] * ua[q] + T[m, q, 1, 1] * ub[q] for q in range(n)])
-                res[m, 0:L] = comb(fa, m)
-                res[m, L:2 * L] = comb(fb, m)
-        for m, c in enumerate(mem):
-            if c >= NS:
-                continue
-            p, i, j = cols[c]
-            wn, we = want[p]
-            ref = np.concatenate([wn[0, i, j], wn[1, i, j], wn[2, i, j], wn[4, i, j], we[3, i, j]])
-            scale = np.array([np.abs(wn[0]).max()] * L + [np.abs(wn[1]).max()] * L + [np.abs(wn[2]).max()] * L
-                             + [np.abs(wn[4]).max()] * L + [max(np.abs(we[3]).max(), 1e-300)] * (L + 1))
-            x = float(np.max(np.abs(res[m] - ref) / scale))
-            worst = x if not np.isfinite(x) or x > worst else worst      # (max(worst, nan) would drop a NaN; one that is kept fails `== 0.0`)
+    for (p, i, j), res in execute_plan(tab, column_lookup(g, owner, rank), L, column_values, ghost):
+        wn, we = want[p]
+        ref = np.concatenate([wn[0, i, j], wn[1, i, j], wn[2, i, j], wn[4, i, j], we[3, i, j]])
+        scale = np.array([np.abs(wn[0]).max()] * L + [np.abs(wn[1]).max()] * L + [np.abs(wn[2]).max()] * L
+                         + [np.abs(wn[4]).max()] * L + [max(np.abs(we[3]).max(), 1e-300)] * (L + 1))
+        x = float(np.max(np.abs(res - ref) / scale))
+        worst = x if not np.isfinite(x) or x > worst else worst      # (max(worst, nan) would drop a NaN; one that is kept fails `== 0.0`)
     e.close()
     q.put((rank, worst, len(send), len(recv)))
     dist.barrier()

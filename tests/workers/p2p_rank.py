@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One rank of a multi-process run with the peer-to-peer halo transport (tmx_halo_p2p_*), for tests/test_gpu_two_process.py and
 tools/p2p_timing.py.  Every rank is its own process; all of them may share HIP device 0 (a 1-GPU box).  The blobs are gathered
-over torch.distributed/gloo on 127.0.0.1.  usage: p2p_rank.py <rank> <world> <port> <outdir> <scheme> <ntracers> <steps> [ne L npatch]"""
+over torch.distributed/gloo on 127.0.0.1.  usage: p2p_rank.py <rank> <world> <port> <outdir> <scheme> <ntracers> <steps> [ne L npatch [owner map]]
+owner map: a name of tests/owner_maps_common.OWNER_MAPS ("reference": round-robin, as the reference deals patches); default: the engine's block map."""
 import os, sys, time
 HERE = os.path.dirname(os.path.abspath(__file__))
 TESTS = os.path.dirname(HERE); ROOT = os.path.dirname(TESTS)
@@ -20,7 +21,11 @@ def main():
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     g, st = gu.make_grid(ne, L, npatch, ntracers=ntr)
-    e = Engine(g, rank=rank, n_ranks=world, device=int(os.environ.get("TMX_TEST_DEVICE", "0")))
+    owner = None
+    if len(sys.argv) > 11:
+        from owner_maps_common import OWNER_MAPS
+        owner = OWNER_MAPS[sys.argv[11]](npatch, world)
+    e = Engine(g, rank=rank, n_ranks=world, owner=owner, device=int(os.environ.get("TMX_TEST_DEVICE", "0")))
     try:
         blobs = [None] * world
         dist.all_gather_object(blobs, e.halo_p2p_export())
