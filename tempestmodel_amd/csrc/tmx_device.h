@@ -4,9 +4,6 @@
 #include "tmx_internal.h"
 #include "tmx_refmath.h"
 
-#ifndef TMX_H_FUSE_W
-#define TMX_H_FUSE_W 1      // W of the interfaces inside a level tile updated by k_h_explicit itself (0: all of them by k_h_w_update)
-#endif
 #ifndef KT_H
 #define KT_H 4      // levels per workgroup of the horizontal kernels (256 threads); 2 / 3 measure the same, 5 / 6 / 8: explicit stage 0.77 / 0.75 / 0.69 against 0.56 ms per step
                     // (three resident wavefronts per SIMD hold whole 4-wavefront workgroups only; taller tiles leave slots empty)
@@ -27,15 +24,6 @@
 #define LU_UPD(a, l, u) ((a) - (l) * (u))
 #else
 #define LU_UPD(a, l, u) __builtin_fma(-(l), (u), (a))
-#endif
-#ifndef TMX_STORE_PRED
-#define TMX_STORE_PRED true
-#endif
-#ifndef TMX_TAIL
-#define TMX_TAIL 2
-#endif
-#ifndef TMX_SEARCH_TREE
-#define TMX_SEARCH_TREE 0      // the tree form of the pivot search costs the pair kernel 8-10 spilled registers
 #endif
 
 #define OPC(op, k, off) p.ops[(((op) * (p.L + 1)) + (k)) * TMX_OPW + ((off) + 2)]
@@ -71,14 +59,6 @@ struct UvTerms { const double * src[12]; const double * xin; };
 // (2 registers + a v_lshl_add_u64) per access.  An instance is 104 MB at ne30 L30; a slab row (NS columns) must
 // stay below 4 GiB of bytes, checked at finalize.
 __device__ __forceinline__ double ldu(const double * uniform_base, unsigned lane_byte_off) {
-	return *(const double *)((const char *)uniform_base + lane_byte_off);
-}
-// the same with the non-temporal hint (TMX_H_TERMS_NT: the raw terms of a stage combination -- up to seven whole instances read once per stage)
-#ifndef TMX_H_TERMS_NT
-#define TMX_H_TERMS_NT 0
-#endif
-__device__ __forceinline__ double ldu_term(const double * uniform_base, unsigned lane_byte_off) {
-	if (TMX_H_TERMS_NT) return __builtin_nontemporal_load((const double *)((const char *)uniform_base + lane_byte_off));
 	return *(const double *)((const char *)uniform_base + lane_byte_off);
 }
 __device__ __forceinline__ void stu(double * uniform_base, unsigned lane_byte_off, double v) {
@@ -127,7 +107,7 @@ __device__ __forceinline__ double base_value_u2(const LinTerms & t, const double
 	if (NT == 0) return ldu(src[0] + slab_off, colb);
 	double x[NT > 0 ? NT : 1];
 #pragma unroll
-	for (int m = 0; m < NT; m++) x[m] = (m > 0 || t.premul) ? ldu_term(src[m] + slab_off, colb) : 0.0;
+	for (int m = 0; m < NT; m++) x[m] = (m > 0 || t.premul) ? ldu(src[m] + slab_off, colb) : 0.0;
 	double v = t.premul ? x[0] * t.coef[0] : 0.0;
 #pragma unroll
 	for (int m = 1; m < NT; m++) v += t.coef[m] * x[m];
@@ -141,7 +121,7 @@ __device__ __forceinline__ double base_value_u(const LinTerms & t, size_t slab_o
 	if (NT == 0) return ldu(t.src[0] + slab_off, colb);
 	double x[NT > 0 ? NT : 1];
 #pragma unroll
-	for (int m = 0; m < NT; m++) x[m] = (m > 0 || t.premul) ? ldu_term(t.src[m] + slab_off, colb) : 0.0;
+	for (int m = 0; m < NT; m++) x[m] = (m > 0 || t.premul) ? ldu(t.src[m] + slab_off, colb) : 0.0;
 	double v = t.premul ? x[0] * t.coef[0] : 0.0;
 #pragma unroll
 	for (int m = 1; m < NT; m++) v += t.coef[m] * x[m];
@@ -154,7 +134,7 @@ __device__ __forceinline__ double base_value_uv(const LinTerms & t, const UvTerm
 	if (NT == 0) return ldu(uv.src[0] + slab_off, colb);
 	double x[NT > 0 ? NT : 1];
 #pragma unroll
-	for (int m = 0; m < NT; m++) x[m] = (m > 0 || t.premul) ? ldu_term(uv.src[m] + slab_off, colb) : 0.0;
+	for (int m = 0; m < NT; m++) x[m] = (m > 0 || t.premul) ? ldu(uv.src[m] + slab_off, colb) : 0.0;
 	double v = t.premul ? x[0] * t.coef[0] : 0.0;
 #pragma unroll
 	for (int m = 1; m < NT; m++) v += t.coef[m] * x[m];
@@ -589,29 +569,14 @@ __device__ __forceinline__ void wave_sync() {
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// workgroup -> (entry of the launch's tile list, level block).  Element-major kernels: the plain 2-D launch.  Node-unique kernels
-// (UQ): a 1-D launch unfolded so that every XCD sweeps a contiguous range of tiles, level block by level block -- neighbouring
-// tiles read the same rows of the unique slabs (the nodes on their common edge), which then come from that XCD's L2.
-// Lane of a wavefront -> position e * 16 + i * 4 + j inside its tile of four elements.  Element-major kernels: the identity (a
-// tile is 512 contiguous bytes of every slab).  Node-unique kernels: lane = j + 4 e + 16 i, so that 16 consecutive lanes hold one
-// node row of the tile's four elements -- for elements that follow one another along beta that is ONE contiguous run of 13
-// unique nodes in the slab (one or two 128-byte lines per 16 lanes); with the identity map a 16-lane group is one element = four
-// runs of 32 bytes in four different rows, four times the L1 / L2 requests per load instruction (measured: 2.1 x the L2 requests
-// of the element-major kernel and +12 % time for 23 % fewer bytes).
-#ifndef TMX_UQ_ROWLANES
-#define TMX_UQ_ROWLANES 0      // measured: with the LDS rows as they were the permuted lanes cost the contractions two-way bank conflicts (hyperviscosity pass 149 ->
-                               // 196 us); with padded rows (lds_pos) the explicit stage is level (0.577 against 0.576 ms per step) and the hyperviscosity pass 4 % slower:
-                               // halving the L2 requests buys nothing, so the identity map stays
-#endif
-// LDS position of tile position l in a contraction row.  With the row-major lane map a half-wavefront holds node rows i = 0, 1 of all
-// four elements, whose 128-byte blocks would fall on the same banks two by two; eight doubles of padding in front of elements 2, 3
-// (rows of 80 instead of 64 doubles) separate them.
-#define TMX_UQ_ROWLEN(UQ_) (((UQ_) && TMX_UQ_ROWLANES) ? 80 : 64)
-template <bool UQ> __device__ __forceinline__ int lds_pos(int l) { return (UQ && TMX_UQ_ROWLANES) ? l + ((l >> 5) << 3) : l; }
-template <bool UQ> __device__ __forceinline__ int tile_lane() {
-	const int h = threadIdx.x;
-	return (UQ && TMX_UQ_ROWLANES) ? ((h & 3) | (((h >> 2) & 3) << 4) | ((h >> 4) << 2)) : h;
-}
+// Lane of a wavefront = position e * 16 + i * 4 + j inside its tile of four elements, in every kernel, and a contraction row of LDS
+// holds a tile's 64 values in that order.  In the node-unique kernels a 16-lane group is then one element = four runs of 32 bytes in
+// four different rows of the slab, four times the L1 / L2 requests per load instruction of the element-major kernel (measured: 2.1 x
+// its L2 requests and +12 % time for 23 % fewer bytes).  The map lane = j + 4 e + 16 i (16 consecutive lanes = one node row of the
+// tile's four elements, one or two 128-byte lines) halves those requests and was measured slower: with the LDS rows as they are the
+// permuted lanes cost the contractions two-way bank conflicts (hyperviscosity pass 149 -> 196 us); with rows padded to 80 doubles
+// the explicit stage is level (0.577 against 0.576 ms per step) and the hyperviscosity pass 4 % slower.  Halving the L2 requests buys
+// nothing (tools/experiments/kernel_build_switches.patch).
 // unique-slab index of the node at position `lane` of tile `tile` (-1: padding), from the tile's eight wave-uniform table entries:
 // no per-lane table load in front of the state loads (a dependent memory round trip at the head of every wavefront: the
 // explicit kernels ran 12 % and the hyperviscosity pass 20 % longer with t_ucol[col] there)
@@ -621,12 +586,12 @@ __device__ __forceinline__ int tile_ucol(const KParams & p, int tile, int lane) 
 	const int b0 = ti[0], b1 = ti[1], b2 = ti[2], b3 = ti[3], n0 = ti[4], n1 = ti[5], n2 = ti[6], n3 = ti[7];
 	const int base = (e == 0) ? b0 : ((e == 1) ? b1 : ((e == 2) ? b2 : b3));
 	const int nj = (e == 0) ? n0 : ((e == 1) ? n1 : ((e == 2) ? n2 : n3));
-#ifdef TMX_ABL_UQ_DLOADS      // ablation builds (wrong results): contiguous addresses instead of the gather, everything else as it is
-	return (base < 0) ? -1 : min(tile * 64 + lane, p.NSS - 1);
-#endif
 	return (base < 0) ? -1 : base + ((lane >> 2) & 3) * nj + (lane & 3);
 }
 
+// workgroup -> (entry of the launch's tile list, level block).  Element-major kernels: the plain 2-D launch.  Node-unique kernels
+// (UQ): a 1-D launch unfolded so that every XCD sweeps a contiguous range of tiles, level block by level block -- neighbouring
+// tiles read the same rows of the unique slabs (the nodes on their common edge), which then come from that XCD's L2.
 template <bool UQ> __device__ __forceinline__ bool wg_tile(const KParams & p, int nyb, int & tile_ix, int & yb) {
 	if (!UQ) { tile_ix = blockIdx.x; yb = blockIdx.y; return true; }
 	if (p.u_xcd) return xcd_tile(p.u_ntiles, nyb, tile_ix, yb);
@@ -648,19 +613,10 @@ static inline dim3 wg_grid(bool uq, const KParams & p, int ntiles, int nyb) {
 //               slot -2 - sdst, k_dss_u finishes the node
 // srow: NV rows of 64 doubles of LDS private to the wavefront.  LDS operations of one wavefront execute in order, so the
 // exchange needs no workgroup barrier; the wavefront-scope fence keeps the compiler from moving the reads above the writes.
-template <int NV, int RL>
-__device__ __forceinline__ void seam_store(const KParams & p, double (*srow)[RL], int lane_, int sdst, int sred, const double (&v)[NV],
+template <int NV>
+__device__ __forceinline__ void seam_store(const KParams & p, double (*srow)[64], int lane, int sdst, int sred, const double (&v)[NV],
 	double * __restrict__ xo, const int (&slab)[NV], int nv)
 {
-	const int lane = lds_pos<RL != 64>(lane_);
-#ifdef TMX_ABL_UQ_DSTORES     // ablation builds (wrong results): every lane stores its own value to consecutive addresses, no exchange
-	{
-		const int c = min((int)(blockIdx.x & 1023) * 64 + lane, p.NSS - 1);
-#pragma unroll
-		for (int t = 0; t < NV; t++) if (t < nv) xo[(size_t)slab[t] * p.NSS + c] = v[t];
-		return;
-	}
-#endif
 #pragma unroll
 	for (int t = 0; t < NV; t++) if (t < nv) srow[t][lane] = v[t];
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -672,11 +628,11 @@ __device__ __forceinline__ void seam_store(const KParams & p, double (*srow)[RL]
 #pragma unroll
 	for (int t = 0; t < NV; t++) o[t] = v[t];
 	if (n == 2) {
-		const int l1 = lds_pos<RL != 64>((sred >> 4) & 63);
+		const int l1 = (sred >> 4) & 63;
 #pragma unroll
 		for (int t = 0; t < NV; t++) if (t < nv) o[t] = 0.5 * (v[t] + srow[t][l1]);
 	} else if (n == 4) {
-		const int l1 = lds_pos<RL != 64>((sred >> 4) & 63), l2 = lds_pos<RL != 64>((sred >> 10) & 63), l3 = lds_pos<RL != 64>((sred >> 16) & 63);
+		const int l1 = (sred >> 4) & 63, l2 = (sred >> 10) & 63, l3 = (sred >> 16) & 63;
 #pragma unroll
 		for (int t = 0; t < NV; t++) if (t < nv) {
 			const double p0 = v[t] + srow[t][l1], p1 = srow[t][l2] + srow[t][l3];

@@ -407,7 +407,7 @@ void tmxk_vi_solve(tmx_engine * e, const KParams & p, const double * xin, double
 // reads 5 KB rows back to back instead of ten 512-byte pieces 389 KB apart.  `AB` below is the lane's pointer into
 // its wavefront's stream (vi_stream_base), NUS / RHS / u are unused by these two helpers.
 #define TMX_UW (TMX_BW + 1)
-// Layout of a U row in the stream (TMX_USTREAM16, default): five 16-byte slots per lane, [row][slot][64 lanes][2] -- one
+// Layout of a U row in the stream: five 16-byte slots per lane, [row][slot][64 lanes][2] -- one
 // global_store_dwordx4 / global_load_dwordx4 moves two entries.  Both phases of the solve are bound by the ISSUE of vector-memory
 // instructions, not by bytes (measured: the producer's five prefetch loads per block row waited 1 000 - 2 800 cycles to
 // issue behind the elimination's ten 8-byte stores per pivot; the back substitution slowed by 30 % when the same bytes were
@@ -417,53 +417,44 @@ void tmxk_vi_solve(tmx_engine * e, const KParams & p, const double * xin, double
 // exist, of the fill-in entries 4..8 a rho*theta row normally has {4,5,7}, a W row {4,6}, a rho row {5}.  Slots 0..2 are
 // always stored; slot 3 / 4 only if one of its two entries is non-zero in some lane (mask bits 3 / 4).  Any other pivot
 // order is still exact, it merely stores a few zeros.
-#ifndef TMX_USTREAM16
-#define TMX_USTREAM16 1
-#endif
 __device__ constexpr int TMX_UPAIR[3][5][2] = {
 	{ { 0, 9 }, { 1, 2 }, { 3, 4 }, { 5, 7 }, { 6, 8 } },      // rho*theta rows
 	{ { 0, 9 }, { 1, 2 }, { 3, 4 }, { 6, 5 }, { 7, 8 } },      // W rows
 	{ { 0, 9 }, { 1, 2 }, { 3, 5 }, { 4, 6 }, { 7, 8 } } };    // rho rows
-#define TMX_USLOT (TMX_USTREAM16 ? 2 : 1)      // doubles per lane and slot
-// TMX_USTREAM_NT: the U-row stream is written once and read once, 5 KB per column and direction -- bit 0: the elimination's stores,
-// bit 1: the back substitution's loads carry the non-temporal hint.  Measured (round 5, ne30 L30, same box, two alternations): the
-// column solve itself does not move (0.476-0.492 ms per step with any of 0..3), but the stream no longer evicts the state from the
-// L2 / Infinity Cache: the explicit kernels that follow go from 0.578 to 0.552 (stores), 0.549 (loads), 0.535 ms per step (both),
-// the step from 1.394 to 1.350 ms.  Default: both -- except in the small-grid variant of the pair kernel (NTS below; profiles/r05_stream_hint_small_grids.txt).
-#ifndef TMX_USTREAM_NT
-#define TMX_USTREAM_NT 3
-#endif
+#define TMX_USLOT 2      // doubles per lane and slot
+// The U-row stream is written once and read once, 5 KB per column and direction: the elimination's stores and the back substitution's
+// loads carry the non-temporal hint.  Measured (round 5, ne30 L30, same box, two alternations): the column solve itself does not move
+// (0.476-0.492 ms per step with the hint on neither, either or both), but the stream no longer evicts the state from the L2 /
+// Infinity Cache: the explicit kernels that follow go from 0.578 to 0.552 (stores only), 0.549 (loads only), 0.535 ms per step (both),
+// the step from 1.394 to 1.350 ms.  So both -- except in the small-grid variant of the pair kernel (NTS below; profiles/r05_stream_hint_small_grids.txt).
 typedef double tmx_dbl2 __attribute__((ext_vector_type(2)));
 // NTS: this instantiation's stream carries the hint at all (the small-grid variant of the pair kernel does not: at ne15 the whole stream, 66 MB,
 // stays in the Infinity Cache between the phases and the hint costs 2 % of the step; at ne20, 125 MB, it already pays)
-#define TMX_NTS_DEFAULT (TMX_USTREAM_NT != 0)
+#define TMX_NTS_DEFAULT true
 template <bool NTS>
 __device__ __forceinline__ void ustream_store2(double * q, double a, double b) {
 	tmx_dbl2 v; v.x = a; v.y = b;
-	if (NTS && (TMX_USTREAM_NT & 1)) __builtin_nontemporal_store(v, (tmx_dbl2 *)q);
+	if (NTS) __builtin_nontemporal_store(v, (tmx_dbl2 *)q);
 	else *(tmx_dbl2 *)q = v;
 }
 template <bool NTS>
 __device__ __forceinline__ double2 ustream_load2(const double * q) {
 	tmx_dbl2 v;
-	if (NTS && (TMX_USTREAM_NT & 2)) v = __builtin_nontemporal_load((const tmx_dbl2 *)q);
+	if (NTS) v = __builtin_nontemporal_load((const tmx_dbl2 *)q);
 	else v = *(const tmx_dbl2 *)q;
 	return make_double2(v.x, v.y);
 }
-// Order of the rows in the scratch (TMX_USTREAM_ROWMAJOR, default): [matrix row][column group][slot][lane] -- the column groups
-// advance through their rows at about the same pace, so at any time the chip writes (elimination) or reads (back substitution)
-// one contiguous run of a few megabytes instead of one 5 KB piece in each of ~800 chunks 476 KB apart.  0: [group][row]....
+// Order of the rows in the scratch: [matrix row][column group][slot][lane] -- the column groups advance through their rows at
+// about the same pace, so at any time the chip writes (elimination) or reads (back substitution) one contiguous run of a few
+// megabytes instead of, with [group][row], one 5 KB piece in each of ~800 chunks 476 KB apart.
 // NUS below is the number of stream columns allocated (64 per column group).
-#ifndef TMX_USTREAM_ROWMAJOR
-#define TMX_USTREAM_ROWMAJOR 1
-#endif
-#define TMX_RS(NUS) (TMX_USTREAM_ROWMAJOR ? (size_t)(NUS) * TMX_UW : (size_t)TMX_UW * 64)      // doubles from one row of a group to its next
-__device__ __forceinline__ double * vi_stream_base(double * AB, int n, int u) {
-	return AB + ((size_t)(u >> 6) * (TMX_USTREAM_ROWMAJOR ? 1 : n) * TMX_UW) * 64 + (u & 63) * TMX_USLOT;
+#define TMX_RS(NUS) ((size_t)(NUS) * TMX_UW)      // doubles from one row of a group to its next
+__device__ __forceinline__ double * vi_stream_base(double * AB, int u) {
+	return AB + ((size_t)(u >> 6) * TMX_UW) * 64 + (u & 63) * TMX_USLOT;
 }
 // the same with the column group and the lane given separately (groups of fewer than 64 columns, k_vi_pair)
-__device__ __forceinline__ double * vi_stream_base_g(double * AB, int n, int grp, int lane) {
-	return AB + ((size_t)grp * (TMX_USTREAM_ROWMAJOR ? 1 : n) * TMX_UW) * 64 + lane * TMX_USLOT;
+__device__ __forceinline__ double * vi_stream_base_g(double * AB, int grp, int lane) {
+	return AB + ((size_t)grp * TMX_UW) * 64 + lane * TMX_USLOT;
 }
 
 // PRED: the sparse stores of the fill-in entries are predicated instead of branched around: the condition "some lane holds a
@@ -476,7 +467,6 @@ template <bool SPARSE, bool PRED, int TYPE, bool NTS = TMX_NTS_DEFAULT>
 __device__ __forceinline__ void lu_store_urow(const double (&piv)[TMX_BW], double pb, double * __restrict__ AB, double * __restrict__ RHS,
 	int jcol, int NUS, int u, int * umask)
 {
-#if TMX_USTREAM16
 	auto val = [&](int e) -> double { return e == 9 ? pb : piv[e]; };
 	double * row = AB + (size_t)jcol * TMX_RS(NUS);
 #pragma unroll
@@ -493,36 +483,6 @@ __device__ __forceinline__ void lu_store_urow(const double (&piv)[TMX_BW], doubl
 		if (PRED ? (any && one) : any) ustream_store2<NTS>(row + sl * 128, a, b);
 	}
 	if (SPARSE ? (threadIdx.x == 0) : true) umask[jcol] = mask;      // dense stores (also the lane-divergent tails, where lane 0 may be masked out): every active lane writes the same word
-#else
-	if (SPARSE && PRED) {
-#pragma unroll
-		for (int c = 0; c < 4; c++) AB[(size_t)jcol * TMX_RS(NUS) + c * 64] = piv[c];
-		AB[(size_t)jcol * TMX_RS(NUS) + TMX_BW * 64] = pb;
-		int one = 1;
-		asm volatile("" : "+v"(one));
-		int mask = 0;
-#pragma unroll
-		for (int c = 4; c < TMX_BW; c++) {
-			const bool any = __builtin_amdgcn_ballot_w64(piv[c] != 0.0) != 0;
-			mask |= any ? (1 << c) : 0;
-			if (any && one) AB[(size_t)jcol * TMX_RS(NUS) + c * 64] = piv[c];
-		}
-		if (threadIdx.x == 0) umask[jcol] = mask;
-		return;
-	}
-#pragma unroll
-	for (int c = 0; c < 4; c++) AB[(size_t)jcol * TMX_RS(NUS) + c * 64] = piv[c];
-	int mask = 0;
-#pragma unroll
-	for (int c = 4; c < TMX_BW; c++) {
-		if (!SPARSE || __builtin_amdgcn_ballot_w64(piv[c] != 0.0) != 0) {
-			AB[(size_t)jcol * TMX_RS(NUS) + c * 64] = piv[c];
-			mask |= 1 << c;
-		}
-	}
-	if (SPARSE ? (threadIdx.x == 0) : true) umask[jcol] = mask;      // dense stores (also the lane-divergent tails, where lane 0 may be masked out): every active lane writes the same word
-	AB[(size_t)jcol * TMX_RS(NUS) + TMX_BW * 64] = pb;
-#endif
 }
 
 // The LDS ring between the two wavefronts of k_vi_pair holds a block row of the column Jacobian WITHOUT its structural zeros:
@@ -572,7 +532,7 @@ __device__ __forceinline__ void lu_pivot_tail_uniform(double (&R)[5][TMX_BW], do
 	double l[5];
 #pragma unroll
 	for (int r = 1; r < 5; r++) l[r] = ((r == PV) ? t0[0] : R[r][0]) * rcp;
-	lu_store_urow<SPARSE, TMX_STORE_PRED, TYPE, NTS>(piv, pb, AB, RHS, jcol, NUS, u, umask);
+	lu_store_urow<SPARSE, true, TYPE, NTS>(piv, pb, AB, RHS, jcol, NUS, u, umask);
 #pragma unroll
 	for (int r = 1; r < 5; r++) {
 		// after the interchange position r holds old row r, except position PV, which holds old row 0
@@ -599,24 +559,13 @@ __device__ __forceinline__ void lu_pivot_step(double (&R)[5][TMX_BW], double (&b
 	const double * inrow, double inb, int * umask, int * n_uniform = nullptr)
 {
 	int pv = 0;
-	if (UNI && TMX_SEARCH_TREE) {
-		// first maximum of |column 0| (dgbtf2's idamax) as a tree: rows 0/1 and 2/3 side by side; strict comparisons keep the
-		// lower row on ties, so the result is the sequential first maximum
-		const double a0 = fabs(R[0][0]), a1 = fabs(R[1][0]), a2 = fabs(R[2][0]), a3 = fabs(R[3][0]), a4 = fabs(R[4][0]);
-		const bool g1 = a1 > a0, g3 = a3 > a2;
-		const double m01 = g1 ? a1 : a0, m23 = g3 ? a3 : a2;
-		const int i01 = g1 ? 1 : 0, i23 = g3 ? 3 : 2;
-		const bool gh = m23 > m01;
-		const double m03 = gh ? m23 : m01;
-		const int i03 = gh ? i23 : i01;
-		pv = (a4 > m03) ? 4 : i03;
-	} else {
-		double amax = fabs(R[0][0]);
+	// first maximum of |column 0| (dgbtf2's idamax), row after row: as a tree (rows 0/1 and 2/3 side by side) the search costs the pair kernel
+	// 8-10 spilled registers
+	double amax = fabs(R[0][0]);
 #pragma unroll
-		for (int r = 1; r < 5; r++) {
-			const double v = fabs(R[r][0]);
-			if (v > amax) { amax = v; pv = r; }
-		}
+	for (int r = 1; r < 5; r++) {
+		const double v = fabs(R[r][0]);
+		if (v > amax) { amax = v; pv = r; }
 	}
 	if (UNI) {
 		const int pv0 = __builtin_amdgcn_readfirstlane(pv);
@@ -633,7 +582,6 @@ __device__ __forceinline__ void lu_pivot_step(double (&R)[5][TMX_BW], double (&b
 				default: lu_pivot_tail_uniform<SPARSE, 4, IS, TYPE, INK, NTS>(R, b, singular, AB, RHS, jcol, NUS, u, inrow, inb, umask); return;
 			}
 		}
-#ifndef TMX_VI_SELECT_PATH
 		// The lanes disagree (rare: neighbouring columns have nearly the same matrix): the same five tails, one pivot row at
 		// a time under the lanes that chose it.  A lane executes exactly the tail of its own pivot row, i.e. the statements
 		// of the per-lane select path below on the same operands; every U-row entry is stored (a fill-in entry that is zero
@@ -646,7 +594,6 @@ __device__ __forceinline__ void lu_pivot_step(double (&R)[5][TMX_BW], double (&b
 		if (pv == 3) lu_pivot_tail_uniform<false, 3, IS, TYPE, INK, NTS>(R, b, singular, AB, RHS, jcol, NUS, u, inrow, inb, umask);
 		if (pv == 4) lu_pivot_tail_uniform<false, 4, IS, TYPE, INK, NTS>(R, b, singular, AB, RHS, jcol, NUS, u, inrow, inb, umask);
 		return;
-#endif
 	}
 #pragma unroll
 	for (int r = 1; r < 5; r++) {
@@ -702,7 +649,6 @@ __device__ __forceinline__ void vi_load_urow(URow & d, int row, int L, size_t NS
 {
 	const int rr = row < 0 ? 0 : row;
 	const int mk = __builtin_amdgcn_readfirstlane(umask[rr]);
-#if TMX_USTREAM16
 	const double * rb = AB + (size_t)rr * TMX_RS(NUS);
 	double2 v[5];
 #pragma unroll
@@ -718,17 +664,6 @@ __device__ __forceinline__ void vi_load_urow(URow & d, int row, int L, size_t NS
 		if (ea == 9) d.y = v[sl].x; else d.u[ea] = v[sl].x;
 		if (eb == 9) d.y = v[sl].y; else d.u[eb] = v[sl].y;
 	}
-#else
-	const double * rb = AB + (size_t)rr * TMX_RS(NUS);
-#pragma unroll
-	for (int c = 0; c < 4; c++) d.u[c] = rb[c * 64];
-#pragma unroll
-	for (int c = 4; c < TMX_BW; c++) {
-		const double * bp = (mk & (1 << c)) ? rb + c * 64 : zp;
-		d.u[c] = bp[0];
-	}
-	d.y = rb[TMX_BW * 64];
-#endif
 	const int k = rr / TMX_FTOT;
 	const int kc = (COMP == 1 || k < L) ? k : L - 1;      // level-L slots of rho*theta / rho have no slab: value unused
 	const int slab = (COMP == 0) ? TMX_SLAB_T(L, kc) : ((COMP == 1) ? TMX_SLAB_W(L, kc) : TMX_SLAB_R(L, kc));
@@ -824,7 +759,7 @@ __global__ __launch_bounds__(64) void k_vi_fused(KParams p, const double * xin, 
 	const int n = TMX_FTOT * (L + 1);
 	const int col = ucol ? ucol[u] : u;      // (null: node-unique layout, a unique column is its own state column)
 	RHS = AB + (size_t)n * TMX_UW * NUS;      // zero page behind the streams (vi_back_substitute)
-	AB = vi_stream_base(AB, n, u);            // this lane's slot in its wavefront's U-row stream
+	AB = vi_stream_base(AB, u);            // this lane's slot in its wavefront's U-row stream
 	ColConst cc;
 	cc.c2a0 = p.g2d[G2_C2A0 * NS + col]; cc.c2a1 = p.g2d[G2_C2A1 * NS + col]; cc.c2b1 = p.g2d[G2_C2B1 * NS + col];
 	cc.jn = p.g2d[G2_JN * NS + col]; cc.je = p.g2d[G2_JE * NS + col]; cc.drx = p.g2d[G2_DRX * NS + col];
@@ -990,10 +925,7 @@ __global__ __launch_bounds__(PAIRS * 64 * (1 + NPROD)) __attribute__((amdgpu_wav
 	// Round 6: WHICH of a CU's two workgroups takes the other order is no longer guessed from blockIdx (it helped only in the runs where the dispatcher
 	// really put workgroups i and i + 256 on one CU: profiles/r06_column_roles_ab.txt) -- a workgroup claims one of two order slots of the CU it finds
 	// itself on (hardware id registers; the slots live behind the engine's flag word) and releases it at its end.
-#ifndef TMX_VI_CU_ORDER
-#define TMX_VI_CU_ORDER 1
-#endif
-	constexpr bool CUORD = TMX_VI_CU_ORDER && PAIRS == 2 && NPROD == 1;
+	constexpr bool CUORD = PAIRS == 2 && NPROD == 1;
 	__shared__ int s_order;
 	const int role0 = (NPROD == 2) ? (wv == 2 ? 1 : 0) : ((PAIRS == 3) ? ((0x31 >> wv) & 1) : (wv & 1)), pair = (NPROD == 2) ? 0 : ((PAIRS == 3) ? ((0x990 >> (2 * wv)) & 3) : (wv >> 1));
 	int * cu_slot = nullptr;
@@ -1028,7 +960,7 @@ __global__ __launch_bounds__(PAIRS * 64 * (1 + NPROD)) __attribute__((amdgpu_wav
 	const int n = TMX_FTOT * (L + 1);
 	const int col = ucol ? ucol[u] : u;      // (null: node-unique layout, a unique column is its own state column)
 	RHS = AB + (size_t)n * TMX_UW * NUS;      // zero page behind the streams (vi_back_substitute)
-	AB = vi_stream_base_g(AB, n, grp, lane);  // this lane's slot in its wavefront's U-row stream
+	AB = vi_stream_base_g(AB, grp, lane);  // this lane's slot in its wavefront's U-row stream
 
 	if (role == 0 && NPROD == 2) {
 		// ---- one of two producers: block rows q, q + 2, ... without the carry; the two levels that enter the window per row are loaded two rows ahead ----
@@ -1295,7 +1227,7 @@ __global__ __launch_bounds__(64 * NSUB) void k_vi_back(KParams p, const double *
 	const int u = (grp * cpw < nunique) ? min(grp * cpw + min(lane, cpw - 1), ulast) : nunique - 1;
 	const int col = ucol ? ucol[u] : u;      // (null: node-unique layout, a unique column is its own state column)
 	const double * RHS = AB + (size_t)n * TMX_UW * NUS;      // zero page behind the streams
-	vi_back_substitute(L, (size_t)p.NS, n, u, col, NUS, vi_stream_base_g(AB, n, grp, lane), RHS, xin, xup, udep, umask_mem, lane);
+	vi_back_substitute(L, (size_t)p.NS, n, u, col, NUS, vi_stream_base_g(AB, grp, lane), RHS, xin, xup, udep, umask_mem, lane);
 }
 
 // ---------------------------------------------------------------------------------------------

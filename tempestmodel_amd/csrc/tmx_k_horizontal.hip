@@ -64,20 +64,6 @@ void tmxk_h_timing_read(unsigned long long * out) { for (int i = 0; i < 128; i++
 #define TMX_H_BURST 0      // 1: raw terms of the stage combination loaded in bursts (lin_load) instead of slab by slab (base_value_u): one memory round trip
                            // instead of five per wavefront, but 185-190 registers (two resident wavefronts per SIMD instead of three): measured equal (element-major) or slower (node-unique)
 #endif
-#ifndef TMX_H_EXNER_LDS
-#define TMX_H_EXNER_LDS 1  // exp / log tables of the Exner function in LDS (one more barrier) instead of two dependent gathers from global memory
-#endif
-#ifndef TMX_H_EM_GROUPS
-#define TMX_H_EM_GROUPS 2
-#endif
-#ifndef TMX_H_LATE_BASE_D
-#define TMX_H_LATE_BASE_D 1      // the same on the element-major layout
-#endif
-#ifndef TMX_H_LATE_BASE
-#define TMX_H_LATE_BASE 1  // node-unique layout, stage combinations of three and more terms: the combination's raw terms are loaded and reduced at the end of
-                           // the kernel, next to the stores, where almost nothing else is live -- in the prologue's burst they take the kernel over 128 registers
-                           // (three resident wavefronts per SIMD instead of four)
-#endif
 // UQ: node-unique state layout (tmx_device.h, seam_store)
 // PM: the update instance enters its own stage combination (LinTerms::premul), a compile-time parameter so that the loads of the
 // combination's raw terms carry no control flow (lin_load)
@@ -91,15 +77,14 @@ template <bool FUSE_V, int NT, bool MF, bool UQ, bool PM, bool EM, bool DM = fal
 __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p, const double * __restrict__ xin,
 	LinTerms xbase, double * xup, double * __restrict__ ucz, double * __restrict__ uv01, double dt, UvTerms uvt, EmitTerms em)
 {
-	__shared__ double s[KT_H][MF ? 1 : 9][TMX_UQ_ROWLEN(UQ)];
+	__shared__ double s[KT_H][MF ? 1 : 9][64];
 	__shared__ double sDw[MF ? 1 : KT_H][16], sSw[MF ? 1 : KT_H][16];      // every wavefront its own copy of the operator tables (no workgroup barrier before the contractions)
-	__shared__ double rmtab[TMX_H_EXNER_LDS ? TMX_RMTAB_DOUBLES : 1];      // exp / log tables of the Exner function: from global memory they are two dependent gathers per wavefront
-	const int lane = tile_lane<UQ>(), ty = WAVE_UNIFORM(threadIdx.y);
+	__shared__ double rmtab[TMX_RMTAB_DOUBLES];      // exp / log tables of the Exner function: from global memory they are two dependent gathers per wavefront
+	const int lane = threadIdx.x, ty = WAVE_UNIFORM(threadIdx.y);      // lane = position e * 16 + i * 4 + j inside the tile, also in an LDS row
 	const int tid = ty * 64 + lane;
-	const int lp = lds_pos<UQ>(lane);      // where this lane's values sit in an LDS row
 	if (!MF && lane < 16) { sDw[ty][lane] = p.dx[lane]; sSw[ty][lane] = p.stiff[lane]; }
 	const double * sD = sDw[MF ? 0 : ty], * sS = sSw[MF ? 0 : ty];
-	if (TMX_H_EXNER_LDS) tmx_rm_tables_to_lds(rmtab, tid, 64 * KT_H);
+	tmx_rm_tables_to_lds(rmtab, tid, 64 * KT_H);
 	const int L = p.L;
 	const size_t NS = (size_t)p.NS;
 	// column of this lane: element-major (e, i, j) in memory; MF: lane = j + 4 e + 16 i
@@ -121,7 +106,10 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 	// and reduced to four values at once -- loading it at the point of use made the compiler keep all 48 LDS reads
 	// and the 4 x NT combination sources live together (180-200 VGPRs, occupancy 2)
 	HT_DECL;
-	constexpr bool LB = TMX_H_LATE_BASE && (UQ || TMX_H_LATE_BASE_D) && FUSE_V && !MF && NT >= 3 && !TMX_H_BURST;
+	// LB: stage combinations of three and more terms (either layout) are loaded and reduced at the end of the kernel, next to the stores, where
+	// almost nothing else is live -- in the prologue's burst their raw terms take the kernel over 128 registers (three resident wavefronts per
+	// SIMD instead of four)
+	constexpr bool LB = FUSE_V && !MF && NT >= 3 && !TMX_H_BURST;
 	double bU = 0, bV = 0, bT = 0, bR = 0, bW = 0;
 	constexpr int NX = NT > 0 ? NT : 1;
 	double xU[NX], xV[NX], xT[NX], xR[NX], xW[NX];
@@ -155,15 +143,15 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 			bV = base_value_u2<NT, true>(xbase, uvt.src, em, TMX_SLAB_V(L, k) * SS, cb, pf); stu(em.xp + TMX_SLAB_V(L, k) * SS, cb, pf);
 			bT = base_value_u2<NT, true>(xbase, xbase.src, em, TMX_SLAB_T(L, k) * SS, cb, pf); stu(em.xp + TMX_SLAB_T(L, k) * SS, cb, pf);
 			bR = base_value_u2<NT, true>(xbase, xbase.src, em, TMX_SLAB_R(L, k) * SS, cb, pf); stu(em.xp + TMX_SLAB_R(L, k) * SS, cb, pf);
-			if (TMX_H_FUSE_W && ty > 0) { bW = base_value_u2<NT, true>(xbase, xbase.src, em, TMX_SLAB_W(L, k) * SS, cb, pf); stu(em.xp + TMX_SLAB_W(L, k) * SS, cb, pf); }
+			if (ty > 0) { bW = base_value_u2<NT, true>(xbase, xbase.src, em, TMX_SLAB_W(L, k) * SS, cb, pf); stu(em.xp + TMX_SLAB_W(L, k) * SS, cb, pf); }
 		} else if (DM) {
 			bU = base_value_dm<NT>(xbase, uvt.src, TMX_SLAB_U(L, k), SS, NS, cb, gb); bV = base_value_dm<NT>(xbase, uvt.src, TMX_SLAB_V(L, k), SS, NS, cb, gb);
 			bT = base_value_dm<NT>(xbase, xbase.src, TMX_SLAB_T(L, k), SS, NS, cb, gb); bR = base_value_dm<NT>(xbase, xbase.src, TMX_SLAB_R(L, k), SS, NS, cb, gb);
-			if (TMX_H_FUSE_W && ty > 0) bW = base_value_dm<NT>(xbase, xbase.src, TMX_SLAB_W(L, k), SS, NS, cb, gb);
+			if (ty > 0) bW = base_value_dm<NT>(xbase, xbase.src, TMX_SLAB_W(L, k), SS, NS, cb, gb);
 		} else {
 			bU = base_value_uv<NT>(xbase, uvt, TMX_SLAB_U(L, k) * SS, cb); bV = base_value_uv<NT>(xbase, uvt, TMX_SLAB_V(L, k) * SS, cb);
 			bT = base_value_u<NT>(xbase, TMX_SLAB_T(L, k) * SS, cb); bR = base_value_u<NT>(xbase, TMX_SLAB_R(L, k) * SS, cb);
-			if (TMX_H_FUSE_W && ty > 0) bW = base_value_u<NT>(xbase, TMX_SLAB_W(L, k) * SS, cb);
+			if (ty > 0) bW = base_value_u<NT>(xbase, TMX_SLAB_W(L, k) * SS, cb);
 		}
 		c2a0 = ldu(p.g2d + G2_C2A0 * NS, gb); c2a1 = ldu(p.g2d + G2_C2A1 * NS, gb); c2b1 = ldu(p.g2d + G2_C2B1 * NS, gb);
 		jn = ldu(p.g2d + G2_JN * NS, gb); j2d = ldu(p.g2d + G2_J2D * NS, gb); fcor = ldu(p.g2d + G2_F * NS, gb);
@@ -209,8 +197,8 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
 	HT_MARK(1);
-	if (TMX_H_EXNER_LDS) __syncthreads();      // the tables are in LDS (every thread's loads are in flight by now)
-	const double exn = act ? (TMX_H_EXNER_LDS ? exner_from_rhotheta_lds(p, rt, rmtab) : exner_from_rhotheta(p, rt)) : 0.0;
+	__syncthreads();      // the tables are in LDS (every thread's loads are in flight by now)
+	const double exn = act ? exner_from_rhotheta_lds(p, rt, rmtab) : 0.0;
 	const double fa = jn * conUa, fb = jn * conUb;
 	double daub = 0, daux = 0, dbua = 0, dbux = 0, dap = 0, dbp = 0, dake = 0, dbke = 0;
 	double darf = 0, dapf = 0, dbrf = 0, dbpf = 0;
@@ -239,26 +227,23 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 			lin_load<NT, PM>(xbase.src, TMX_SLAB_T(L, k) * SS, cb2, xT); lin_load<NT, PM>(xbase.src, TMX_SLAB_R(L, k) * SS, cb2, xR);
 		}
 	} else {
-	s[ty][0][lp] = ua;  s[ty][1][lp] = ub;  s[ty][2][lp] = ux;
-	s[ty][3][lp] = exn; s[ty][4][lp] = ke;
-	s[ty][5][lp] = fa * rh; s[ty][6][lp] = fa * rt;
-	s[ty][7][lp] = fb * rh; s[ty][8][lp] = fb * rt;
+	s[ty][0][lane] = ua;  s[ty][1][lane] = ub;  s[ty][2][lane] = ux;
+	s[ty][3][lane] = exn; s[ty][4][lane] = ke;
+	s[ty][5][lane] = fa * rh; s[ty][6][lane] = fa * rt;
+	s[ty][7][lane] = fb * rh; s[ty][8][lane] = fb * rt;
 	wave_sync();      // the rows are this wavefront's own
 	HT_MARK(2);
 	if (!act) return;
-#ifdef TMX_H_SCHED_BARRIER
-	__builtin_amdgcn_sched_barrier(0);
-#endif
 	// what the thread does with its results (seam_store): loaded behind the barrier, when the registers of the prologue are free
 	// again (in front of it they cost the first stage's kernel its fourth wavefront per SIMD), used at the end
 	if (UQ) { sdst = p.t_sdst[col]; sred = p.t_sred[col]; }
 	if (TMX_H_BURST) {
 		const unsigned cb2 = (unsigned)uc * 8u;
 		lin_load<NT, PM>(xbase.src, TMX_SLAB_T(L, k) * SS, cb2, xT); lin_load<NT, PM>(xbase.src, TMX_SLAB_R(L, k) * SS, cb2, xR);
-		if (TMX_H_FUSE_W && ty > 0) lin_load<NT, PM>(xbase.src, TMX_SLAB_W(L, k) * SS, cb2, xW);
+		if (ty > 0) lin_load<NT, PM>(xbase.src, TMX_SLAB_W(L, k) * SS, cb2, xW);
 	}
 
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lds_pos<UQ>(lane & 48);
+	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
 #pragma unroll
 	for (int t = 0; t < 4; t++) {
 		const int la = eb + 4 * t + j;        // node (t, j)
@@ -335,7 +320,7 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 	}
 	if (TMX_H_BURST) {
 		bT = lin_reduce<NT, PM>(xbase, xT); bR = lin_reduce<NT, PM>(xbase, xR);
-		if (TMX_H_FUSE_W && ty > 0) bW = lin_reduce<NT, PM>(xbase, xW);
+		if (ty > 0) bW = lin_reduce<NT, PM>(xbase, xW);
 	}
 	const double tR = dt * invJ * (darf + dbrf), tT = dt * invJ * (dapf + dbpf);
 	double outR = bR - tR, outT = bT - tT;
@@ -346,38 +331,30 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 		stu(xup + sT, colb, outT);
 	}
 	double outW = 0.0, tW = 0.0;
-	if (TMX_H_FUSE_W) {
-		// (MF: the matrix-unit variant keeps one 512-byte row per wavefront for exactly this hand-over; round 3 measured it without,
-		// i.e. with every interface left to k_h_w_update)
-		// W on the interfaces inside the tile (part 2 below, :1612-1659): interface k takes (u x zeta)_xi of the levels k - 1 and k,
-		// which wavefront ty - 1 hands over through its own (now free) LDS row; only the tile's first interface is left to
-		// k_h_w_update, which therefore needs the hand-off array for the first and the last level of a tile only
-		s[ty][0][lp] = uczx;
-		if (ty == 0 || ty == KT_H - 1) stu(ucz + (size_t)k * NS, colb, uczx);
-		HT_MARK(4);
-		__syncthreads();       // wavefronts above the top level have left; the barrier counts the ones still running
-		HT_MARK(5);
-		if (ty > 0) {
-			double v = 0.0;
-			v += OPC(TMX_OP_INTERP_NODE_TO_REDGE, k, -1) * s[ty - 1][0][lp];
-			v += OPC(TMX_OP_INTERP_NODE_TO_REDGE, k, 0) * uczx;
-			tW = dt * v;
-			outW = bW + tW;
-			if (!UQ && !LB) stu(xup + TMX_SLAB_W(L, k) * NS, colb, outW);
-		}
-	} else
-		stu(ucz + (size_t)k * NS, colb, uczx);
+	// (MF: the matrix-unit variant keeps one 512-byte row per wavefront for exactly this hand-over; round 3 measured it without,
+	// i.e. with every interface left to k_h_w_update)
+	// W on the interfaces inside the tile (part 2 below, :1612-1659): interface k takes (u x zeta)_xi of the levels k - 1 and k,
+	// which wavefront ty - 1 hands over through its own (now free) LDS row; only the tile's first interface is left to
+	// k_h_w_update, which therefore needs the hand-off array for the first and the last level of a tile only
+	s[ty][0][lane] = uczx;
+	if (ty == 0 || ty == KT_H - 1) stu(ucz + (size_t)k * NS, colb, uczx);
+	HT_MARK(4);
+	__syncthreads();       // wavefronts above the top level have left; the barrier counts the ones still running
+	HT_MARK(5);
+	if (ty > 0) {
+		double v = 0.0;
+		v += OPC(TMX_OP_INTERP_NODE_TO_REDGE, k, -1) * s[ty - 1][0][lane];
+		v += OPC(TMX_OP_INTERP_NODE_TO_REDGE, k, 0) * uczx;
+		tW = dt * v;
+		outW = bW + tW;
+		if (!UQ && !LB) stu(xup + TMX_SLAB_W(L, k) * NS, colb, outW);
+	}
 	if (LB) {
 		// the stage combination, now: NT loads per slab in flight beside five increments (and, EM, the prefix of a later stage's
 		// combination formed from the same terms: every copy of a node forms the same one and stores it, to the same entry)
-#if TMX_H_LATE_BASE == 2
-		__builtin_amdgcn_sched_barrier(0);
-#endif
 		unsigned cb = (unsigned)uc * 8u;
-#if TMX_H_LATE_BASE == 1
 		asm volatile("" : "+v"(cb) : "v"(tR), "v"(tT), "v"(outU), "v"(outV));      // (the addresses exist only now: the loads cannot be moved up into the contractions)
-#endif
-		const bool withW = TMX_H_FUSE_W && ty > 0;
+		const bool withW = ty > 0;
 		double pU = 0, pV = 0, pT = 0, pR = 0, pW = 0;
 		if (DM) {
 			unsigned gbl = (unsigned)col * 8u;
@@ -388,14 +365,9 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 		} else {
 		bU = base_value_u2<NT, EM>(xbase, uvt.src, em, TMX_SLAB_U(L, k) * SS, cb, pU);
 		bV = base_value_u2<NT, EM>(xbase, uvt.src, em, TMX_SLAB_V(L, k) * SS, cb, pV);
-#if TMX_H_EM_GROUPS >= 2
-		// EM: both sums need a slab's terms, and all five slabs' terms in flight at once cost the fourth resident wavefront again: two (three) rounds
+		// EM: both sums need a slab's terms, and all five slabs' terms in flight at once cost the fourth resident wavefront again: two rounds
 		if (EM) asm volatile("" : "+v"(cb) : "v"(bU), "v"(bV), "v"(pU), "v"(pV));
-#endif
 		bT = base_value_u2<NT, EM>(xbase, xbase.src, em, TMX_SLAB_T(L, k) * SS, cb, pT);
-#if TMX_H_EM_GROUPS >= 3
-		if (EM) asm volatile("" : "+v"(cb) : "v"(bT), "v"(pT));
-#endif
 		bR = base_value_u2<NT, EM>(xbase, xbase.src, em, TMX_SLAB_R(L, k) * SS, cb, pR);
 		if (withW) bW = base_value_u2<NT, EM>(xbase, xbase.src, em, TMX_SLAB_W(L, k) * SS, cb, pW);
 		}
@@ -419,7 +391,7 @@ __global__ __launch_bounds__(64 * KT_H, TMX_H_MINWG) void k_h_explicit(KParams p
 		// rows 1..5 of the wavefront's LDS block (row 0 is being read by the wavefront above); W only where this kernel updates it
 		const double v[5] = { outU, outV, outR, outT, outW };
 		const int slab[5] = { TMX_SLAB_U(L, k), TMX_SLAB_V(L, k), TMX_SLAB_R(L, k), TMX_SLAB_T(L, k), TMX_SLAB_W(L, k) };
-		seam_store<5, TMX_UQ_ROWLEN(UQ)>(p, &s[ty][1], lane, sdst, sred, v, xup, slab, (TMX_H_FUSE_W && ty > 0) ? 5 : 4);
+		seam_store<5>(p, &s[ty][1], lane, sdst, sred, v, xup, slab, (ty > 0) ? 5 : 4);
 	}
 #ifdef TMX_H_TIMING
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -443,7 +415,7 @@ __global__ __launch_bounds__(256) void k_h_w_update(KParams p, LinTerms xbase, d
 	int tix, yb;
 	const int nfirst = (L + stride - 1) / stride;          // interfaces idx * stride < L, then the top one
 	if (!wg_tile<UQ>(p, (nfirst + 1 + 3) / 4, tix, yb)) return;
-	const int lane = tile_lane<UQ>();
+	const int lane = threadIdx.x;
 	const int tile = p.quads ? p.quads[tix] : tix;
 	const int col = tile * 64 + lane;
 	const int idx = yb * 4 + ty;
@@ -497,7 +469,7 @@ __global__ __launch_bounds__(256) void k_h_w_update(KParams p, LinTerms xbase, d
 	if (UQ) {
 		const double v1[1] = { wnew };
 		const int slab[1] = { TMX_SLAB_W(L, k) };
-		seam_store<1, 64>(p, &sw[ty][0], lane, p.t_sdst[col], p.t_sred[col], v1, xup, slab, 1);
+		seam_store<1>(p, &sw[ty][0], lane, p.t_sdst[col], p.t_sred[col], v1, xup, slab, 1);
 	} else
 		xup[TMX_SLAB_W(L, k) * NS + col] = wnew;
 }
@@ -519,8 +491,7 @@ void tmxk_h_explicit(tmx_engine * e, const KParams & p, const StageIO & st) {
 	// copy-by-copy reads of element-major sources exist in the node-unique kernels with the vertical part fused in only
 	if (dmask && !(uq && fuse_v)) { tmx_set_error("internal: explicit stage with element-major sources outside the fused node-unique kernels"); hipMemsetAsync(e->d_flag, 0xff, sizeof(int), e->stream); return; }
 	KParams q = p; q.u_ntiles = ntile;
-	const int wstride = TMX_H_FUSE_W ? KT_H : 1;
-	const int nyb = (p.L + KT_H - 1) / KT_H, nyb2 = ((p.L + wstride - 1) / wstride + 1 + 3) / 4;
+	const int nyb = (p.L + KT_H - 1) / KT_H, nyb2 = (nyb + 1 + 3) / 4;      // (k_h_w_update: the first interface of every level tile and the top one)
 	dim3 blk(64, KT_H), grd = wg_grid(uq, q, ntile, nyb);
 	double * uv01 = e->d_scratch + (size_t)p.L * p.NS;     // 4 slabs behind the (u x zeta)_xi hand-off
 	dim3 blk2(64, 4), grd2 = wg_grid(uq, q, ntile, nyb2);
@@ -540,10 +511,10 @@ void tmxk_h_explicit(tmx_engine * e, const KParams & p, const StageIO & st) {
 		else if (fuse_v) hipLaunchKernelGGL((k_h_explicit<true, NT_, false, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
 		else hipLaunchKernelGGL((k_h_explicit<false, NT_, false, false, PM_, false>), grd, blk, 0, e->stream, p, xin, xbase, xup, e->d_scratch, uv01, dt, uvt, em0);
 		// ... and W of the interfaces the stage's kernel left
-		if (TMX_EXP && uq && emit_ok && NT_ >= 3 && NT_ <= 8) hipLaunchKernelGGL((k_h_w_update<(NT_ >= 3 && NT_ <= 8) ? NT_ : 3, true, TMX_EXP != 0>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em);
-		else if (uq && dmask) hipLaunchKernelGGL((k_h_w_update<NT_, true, false, true>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0);
-		else if (uq) hipLaunchKernelGGL((k_h_w_update<NT_, true, false>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0);
-		else hipLaunchKernelGGL((k_h_w_update<NT_, false, false>), grd2, blk2, 0, e->stream, p, xbase, xup, (const double *)e->d_scratch, uvp, dt, wstride, em0);
+		if (TMX_EXP && uq && emit_ok && NT_ >= 3 && NT_ <= 8) hipLaunchKernelGGL((k_h_w_update<(NT_ >= 3 && NT_ <= 8) ? NT_ : 3, true, TMX_EXP != 0>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, KT_H, em);
+		else if (uq && dmask) hipLaunchKernelGGL((k_h_w_update<NT_, true, false, true>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, KT_H, em0);
+		else if (uq) hipLaunchKernelGGL((k_h_w_update<NT_, true, false>), grd2, blk2, 0, e->stream, q, xbase, xup, (const double *)e->d_scratch, uvp, dt, KT_H, em0);
+		else hipLaunchKernelGGL((k_h_w_update<NT_, false, false>), grd2, blk2, 0, e->stream, p, xbase, xup, (const double *)e->d_scratch, uvp, dt, KT_H, em0);
 	});
 }
 
@@ -877,12 +848,11 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 {
 	// every LDS row here belongs to one wavefront (its level's fields, its own copy of the operator tables): the kernel has no
 	// workgroup barrier, the four wavefronts of a workgroup run decoupled (wave_sync) -- up to the one exchange of the block form
-	__shared__ double s[4][8][TMX_UQ_ROWLEN(UQ)];
+	__shared__ double s[4][8][64];
 	__shared__ double sDw[4][16], sSw[4][16];
 	__shared__ double xs[BLK ? 5 : 1][BLK ? 256 : 1];
-	const int lane = tile_lane<UQ>(), ty = WAVE_UNIFORM(threadIdx.y);
+	const int lane = threadIdx.x, ty = WAVE_UNIFORM(threadIdx.y);
 	if (lane < 16) { sDw[ty][lane] = p.dx[lane]; sSw[ty][lane] = p.stiff[lane]; }
-	const int lp = lds_pos<UQ>(lane);
 	const int L = p.L;
 	const size_t NS = (size_t)p.NS;
 	int tix, yb;
@@ -900,7 +870,7 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 	const bool here = UQ ? (uc >= 0) : (col < p.ncol);
 	const bool actw = (kk <= L) && here;     // interface level (W)
 	const bool actn = (kk < L) && here;      // model level (U,V,rho*theta,rho)
-	const ElPos ep = el_pos(lane, lds_pos<UQ>(lane & 48));
+	const ElPos ep = el_pos(lane, lane & 48);
 
 	double psiT = 0, psiR = 0, psiW = 0, ua = 0, ub = 0;
 	double c2a0 = 0, c2a1 = 0, c2b1 = 0, j2d = 1, jn = 1, je = 1;
@@ -939,9 +909,9 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 		}
 	}
 	const ElPair ju = el_flux(j2d, c2a0, c2a1, c2b1, ua, ub);
-	s[ty][0][lp] = psiT; s[ty][1][lp] = psiR; s[ty][2][lp] = psiW;
-	s[ty][3][lp] = ua;   s[ty][4][lp] = ub;
-	s[ty][5][lp] = ju.a; s[ty][6][lp] = ju.b;
+	s[ty][0][lane] = psiT; s[ty][1][lane] = psiR; s[ty][2][lane] = psiW;
+	s[ty][3][lane] = ua;   s[ty][4][lane] = ub;
+	s[ty][5][lane] = ju.a; s[ty][6][lane] = ju.b;
 	wave_sync();
 
 	// gradients of rho*theta, rho, W; d_alpha U_beta, d_beta U_alpha; d_alpha (J U^alpha), d_beta (J U^beta)
@@ -955,10 +925,10 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 	// what the thread does with its results (seam_store): loaded here, behind the first contraction, used at the end
 	const int sdst = UQ ? (BLK ? p.b_sdst[col] : p.t_sdst[col]) : 0, sred = UQ ? (BLK ? p.b_sred[col] : p.t_sred[col]) : 0;
 	wave_sync();
-	s[ty][0][lp] = fT.a; s[ty][1][lp] = fT.b;
-	s[ty][2][lp] = fR.a; s[ty][3][lp] = fR.b;
-	s[ty][4][lp] = fW.a; s[ty][5][lp] = fW.b;
-	s[ty][6][lp] = dc.a; s[ty][7][lp] = dc.b;
+	s[ty][0][lane] = fT.a; s[ty][1][lane] = fT.b;
+	s[ty][2][lane] = fR.a; s[ty][3][lane] = fR.b;
+	s[ty][4][lane] = fW.a; s[ty][5][lane] = fW.b;
+	s[ty][6][lane] = dc.a; s[ty][7][lane] = dc.b;
 	wave_sync();
 	if (!BLK && !actw) return;      // (BLK: padding lanes stay for the exchange below -- a whole padding wavefront must reach the barrier its block's others wait at)
 
@@ -981,7 +951,7 @@ __global__ __launch_bounds__(256, (UQ && TMX_HV_MINWG < 4) ? 4 : TMX_HV_MINWG) v
 		const double v[5] = { oW, oT, oR, oU, oV };
 		const int slab[5] = { TMX_SLAB_W(L, kk), TMX_SLAB_T(L, kk), TMX_SLAB_R(L, kk), TMX_SLAB_U(L, kk), TMX_SLAB_V(L, kk) };
 		if constexpr (BLK) block_seam_store<5>(p, xs, ty * 64 + lane, sdst, sred, v, xout, slab, (kk < L) ? 31u : 1u);
-		else seam_store<5, TMX_UQ_ROWLEN(UQ)>(p, &s[ty][0], lane, sdst, sred, v, xout, slab, (kk < L) ? 5 : 1);
+		else seam_store<5>(p, &s[ty][0], lane, sdst, sred, v, xout, slab, (kk < L) ? 5 : 1);
 		return;
 	}
 	xout[TMX_SLAB_W(L, kk) * NS + col] = oW;

@@ -51,7 +51,7 @@ void tmxk_h_walk_timing_read(unsigned long long * out) { for (int i = 0; i < 128
 template <bool DM>
 __device__ __forceinline__ double term_load(const double * src, unsigned dmask, int m, int slab, size_t SS, size_t NS, unsigned cb, unsigned gb) {
 	const bool d = DM && ((dmask >> m) & 1u);
-	return ldu_term(src + (size_t)slab * (d ? NS : SS), d ? gb : cb);
+	return ldu(src + (size_t)slab * (d ? NS : SS), d ? gb : cb);
 }
 
 template <int NT, bool PM, bool DM>
@@ -138,16 +138,14 @@ template <int NT, bool PM, bool DM, bool BLK = false, bool EM = false, bool UQ =
 __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(KParams p, const double * __restrict__ xin, LinTerms xbase, double * xup, double dt, UvTerms uvt, int nseg, EmitTerms em,
 	UdiffArgs ud)
 {
-	constexpr int RL = TMX_UQ_ROWLEN(true);
 	constexpr int NW = BLK ? 4 : 1;
-	__shared__ double sw[NW][9][RL];
+	__shared__ double sw[NW][9][64];
 	__shared__ double xs[BLK ? 2 : 1][BLK ? 6 : 1][BLK ? 256 : 1];
 	__shared__ double sD[16], sS[16];
 	__shared__ double rmtab[TMX_RMTAB_DOUBLES];
 	const int wv = BLK ? WAVE_UNIFORM(threadIdx.y) : 0;
-	double (*s)[RL] = sw[wv];
-	const int lane = tile_lane<true>();      // position e * 16 + i * 4 + j of this thread inside its tile (tmx_device.h: the identity unless TMX_UQ_ROWLANES)
-	const int lp = lds_pos<true>(lane);      // where its values sit in an LDS row
+	double (*s)[64] = sw[wv];
+	const int lane = threadIdx.x;      // position e * 16 + i * 4 + j of this thread inside its tile, and where its values sit in an LDS row
 	HW_DECL;
 	// the exp / log tables (256 + 256 words) on their way to LDS: a lane's loads in flight with the geometry and the first window
 	constexpr int NTL = BLK ? 1 : 4;
@@ -208,7 +206,7 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 	const double wH = (k0 > 0) ? ldu(xin + TMX_SLAB_W(L, k0 - 1) * SX, cx) : 0.0;
 	const double invJ = 1.0 / jn;
 	const double fj = fcor * j2d;
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lds_pos<true>(lane & 48);
+	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
 	if (tidw < 16) { sD[tidw] = p.dx[tidw]; sS[tidw] = p.stiff[tidw]; }
 #pragma unroll
 	for (int t = 0; t < NTL; t++) { rmtab[t * 64 + tidw] = tlog[t]; ((unsigned long long *)(rmtab + 256))[t * 64 + tidw] = texp[t]; }
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 		double ux = 0.0; ux += OPK(TMX_OP_INTERP_REDGE_TO_NODE, kh, 0) * wH; ux += OPK(TMX_OP_INTERP_REDGE_TO_NODE, kh, 1) * w0;
 		const double conUa = c2a0 * uM + c2a1 * vM + ca2 * ux;
 		const double conUb = c2a1 * uM + c2b1 * vM + cb2 * ux;
-		s[2][lp] = ux;
+		s[2][lane] = ux;
 		wave_sync();
 		double daux = 0, dbux = 0;
 #pragma unroll
@@ -302,10 +300,10 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 		const double ke = 0.5 * (conUa * u0 + conUb * v0 + conUx * ux);
 		const double exn = exner_from_rhotheta_lds(p, t0, rmtab);
 		const double fa = jn * conUa, fb = jn * conUb;
-		s[0][lp] = u0;  s[1][lp] = v0;  s[2][lp] = ux;
-		s[3][lp] = exn; s[4][lp] = ke;
-		s[5][lp] = fa * r0; s[6][lp] = fa * t0;
-		s[7][lp] = fb * r0; s[8][lp] = fb * t0;
+		s[0][lane] = u0;  s[1][lane] = v0;  s[2][lane] = ux;
+		s[3][lane] = exn; s[4][lane] = ke;
+		s[5][lane] = fa * r0; s[6][lane] = fa * t0;
+		s[7][lane] = fb * r0; s[8][lane] = fb * t0;
 		wave_sync();
 		HW_MARK(2);
 		// the twelve 4 x 4 contractions in four groups of three (each sum in the level-parallel kernel's order, t = 0 .. 3); the empty asm
@@ -420,8 +418,8 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 			// count of 10 of the 36 instantiations and the scratch of one; profiles/viscosity_operators_statement_list.md)
 			wave_sync();
 			const double psiT = t0 - rfT, psiW = w0 - rfW;
-			s[0][lp] = psiT; s[1][lp] = psiW;
-			s[2][lp] = u0; s[3][lp] = v0; s[4][lp] = j2d * (c2a0 * u0 + c2a1 * v0); s[5][lp] = j2d * (c2a1 * u0 + c2b1 * v0);
+			s[0][lane] = psiT; s[1][lane] = psiW;
+			s[2][lane] = u0; s[3][lane] = v0; s[4][lane] = j2d * (c2a0 * u0 + c2a1 * v0); s[5][lane] = j2d * (c2a1 * u0 + c2b1 * v0);
 			wave_sync();
 			double daT = 0, dbT = 0, daW = 0, dbW = 0;
 			double dUb = 0, dbUa = 0, dajua = 0, dbjub = 0;
@@ -439,9 +437,9 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 			const double invJ2 = 1.0 / j2d;
 			const double dv = (dajua + dbjub) * invJ2, cl = (dUb - dbUa) * invJ2;
 			wave_sync();
-			s[0][lp] = jn * (c2a0 * daT + c2a1 * dbT); s[1][lp] = jn * (c2a1 * daT + c2b1 * dbT);
-			s[2][lp] = je * (c2a0 * daW + c2a1 * dbW); s[3][lp] = je * (c2a1 * daW + c2b1 * dbW);
-			s[4][lp] = dv; s[5][lp] = cl;
+			s[0][lane] = jn * (c2a0 * daT + c2a1 * dbT); s[1][lane] = jn * (c2a1 * daT + c2b1 * dbT);
+			s[2][lane] = je * (c2a0 * daW + c2a1 * dbW); s[3][lane] = je * (c2a1 * daW + c2b1 * dbW);
+			s[4][lane] = dv; s[5][lane] = cl;
 			wave_sync();
 			double uaT = 0, ubT = 0, uaW = 0, ubW = 0, dad = 0, dbd = 0, dac = 0, dbc = 0;
 #pragma unroll
@@ -530,7 +528,7 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 			{
 				const double v[5] = { outU, outV, outR, outT, outW };
 				const int slab[5] = { TMX_SLAB_U(L, k), TMX_SLAB_V(L, k), TMX_SLAB_R(L, k), TMX_SLAB_T(L, k), TMX_SLAB_W(L, k) };
-				seam_store<5, RL>(p, &s[0], lane, sdst, sred, v, xup, slab, (k > 0) ? 5 : 4);
+				seam_store<5>(p, &s[0], lane, sdst, sred, v, xup, slab, (k > 0) ? 5 : 4);
 			}
 			if (k == 0) { uh0 = uh; vh0 = vh; }
 			if (k == 1) {
@@ -543,7 +541,7 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 				met_eval(mc, etac[L], e0, e1, e2, ea, eb_);
 				const double v1[1] = { -(e0 * ub0 + e1 * vb0) / e2 };
 				const int slab1[1] = { TMX_SLAB_W(L, 0) };
-				seam_store<1, RL>(p, &s[0], lane, sdst, sred, v1, xup, slab1, 1);
+				seam_store<1>(p, &s[0], lane, sdst, sred, v1, xup, slab1, 1);
 			}
 		}
 		wave_sync();
@@ -565,14 +563,14 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 				// the lid's W diffuses too (k_uniform_diffusion's interface L: W alone); w0 holds the initial W of the lid after the last slide
 				const double psiW = w0 - ldu(ud.xref + TMX_SLAB_W(L, L) * NS, cb);
 				wave_sync();
-				s[1][lp] = psiW;
+				s[1][lane] = psiW;
 				wave_sync();
 				double daW = 0, dbW = 0;
 #pragma unroll
 				for (int t = 0; t < 4; t++) { daW += s[1][eb + 4 * t + j] * sD[t * 4 + i]; dbW += s[1][eb + 4 * i + t] * sD[t * 4 + j]; }
 				daW *= ida; dbW *= idb;
 				wave_sync();
-				s[2][lp] = je * (c2a0 * daW + c2a1 * dbW); s[3][lp] = je * (c2a1 * daW + c2b1 * dbW);
+				s[2][lane] = je * (c2a0 * daW + c2a1 * dbW); s[3][lane] = je * (c2a1 * daW + c2b1 * dbW);
 				wave_sync();
 				double uaW = 0, ubW = 0;
 #pragma unroll
@@ -585,7 +583,7 @@ __global__ __launch_bounds__(BLK ? 256 : 64, TMX_HW_WAVES_PER_EU) void k_h_walk(
 		}
 		if (EM) stu(em.xp + TMX_SLAB_W(L, L) * SS, cb, emit_value<NT>(em, xW));
 		const int slab1[1] = { TMX_SLAB_W(L, L) };
-		seam_store<1, RL>(p, &s[0], lane, sdst, sred, v1, xup, slab1, 1);
+		seam_store<1>(p, &s[0], lane, sdst, sred, v1, xup, slab1, 1);
 	}
 	HW_MARK(6);
 	HW_END(NT);
@@ -721,10 +719,9 @@ template <bool HB>
 __global__ __launch_bounds__(64, 4) void k_hv_walk(KParams p, const double * __restrict__ xsrc, const double * __restrict__ xbase, double * __restrict__ xout,
 	double dt, double nu_s_in, double nu_d_in, double nu_v_in, int scale, int nseg)
 {
-	constexpr int RL = TMX_UQ_ROWLEN(true);
-	__shared__ double s[8][RL];
+	__shared__ double s[8][64];
 	__shared__ double sD[16], sS[16];
-	const int lane = tile_lane<true>(), lp = lds_pos<true>(lane);
+	const int lane = threadIdx.x;
 	if (threadIdx.x < 16) { sD[threadIdx.x] = p.dx[threadIdx.x]; sS[threadIdx.x] = p.stiff[threadIdx.x]; }
 	const int L = p.L;
 	const size_t NS = (size_t)p.NS, SS = (size_t)p.NSS;
@@ -748,7 +745,7 @@ __global__ __launch_bounds__(64, 4) void k_hv_walk(KParams p, const double * __r
 	const double nu_s = nu_s_in * nsc, nu_d = nu_d_in * nsc, nu_v = nu_v_in * nsc;
 	const int sdst = p.t_sdst[col], sred = p.t_sred[col];
 	const double invJ2 = 1.0 / j2d, invJ = 1.0 / jn, rje = 1.0 / je;
-	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lds_pos<true>(lane & 48);
+	const int q = lane & 15, i = q >> 2, j = q & 3, eb = lane & 48;
 	// a level's fields: W of interface k and, below the lid, rho*theta, rho, U, V of level k (a level >= L has W alone: the others re-read level L - 1,
 	// unused); padding lanes read node 0 and store nothing.  Every load unconditional, so that the loads in flight can be counted (s_waitcnt vmcnt(n)).
 	struct Lev { double W, T, R, U, V, bW, bT, bR, bU, bV; };
@@ -774,9 +771,9 @@ __global__ __launch_bounds__(64, 4) void k_hv_walk(KParams p, const double * __r
 		const double psiT = actn ? c.T : 0.0, psiR = actn ? c.R : 0.0, ua = actn ? c.U : 0.0, ub = actn ? c.V : 0.0, psiW = c.W;
 		const double cua = c2a0 * ua + c2a1 * ub;
 		const double cub = c2a1 * ua + c2b1 * ub;
-		s[0][lp] = psiT; s[1][lp] = psiR; s[2][lp] = psiW;
-		s[3][lp] = ua;   s[4][lp] = ub;
-		s[5][lp] = j2d * cua; s[6][lp] = j2d * cub;
+		s[0][lane] = psiT; s[1][lane] = psiR; s[2][lane] = psiW;
+		s[3][lane] = ua;   s[4][lane] = ub;
+		s[5][lane] = j2d * cua; s[6][lane] = j2d * cub;
 		wave_sync();
 		double daT = 0, dbT = 0, daR = 0, dbR = 0, daW = 0, dbW = 0, daub = 0, dbua = 0, dajua = 0, dbjub = 0;
 #pragma unroll
@@ -793,10 +790,10 @@ __global__ __launch_bounds__(64, 4) void k_hv_walk(KParams p, const double * __r
 		daub *= ida; dbua *= idb; dajua *= ida; dbjub *= idb;
 		const double dv = (dajua + dbjub) * invJ2, cl = (daub - dbua) * invJ2;
 		wave_sync();
-		s[0][lp] = jn * (c2a0 * daT + c2a1 * dbT); s[1][lp] = jn * (c2a1 * daT + c2b1 * dbT);
-		s[2][lp] = jn * (c2a0 * daR + c2a1 * dbR); s[3][lp] = jn * (c2a1 * daR + c2b1 * dbR);
-		s[4][lp] = je * (c2a0 * daW + c2a1 * dbW); s[5][lp] = je * (c2a1 * daW + c2b1 * dbW);
-		s[6][lp] = dv; s[7][lp] = cl;
+		s[0][lane] = jn * (c2a0 * daT + c2a1 * dbT); s[1][lane] = jn * (c2a1 * daT + c2b1 * dbT);
+		s[2][lane] = jn * (c2a0 * daR + c2a1 * dbR); s[3][lane] = jn * (c2a1 * daR + c2b1 * dbR);
+		s[4][lane] = je * (c2a0 * daW + c2a1 * dbW); s[5][lane] = je * (c2a1 * daW + c2b1 * dbW);
+		s[6][lane] = dv; s[7][lane] = cl;
 		wave_sync();
 		double uaT = 0, ubT = 0, uaR = 0, ubR = 0, uaW = 0, ubW = 0, dad = 0, dbd = 0, dac = 0, dbc = 0;
 #pragma unroll
@@ -829,7 +826,7 @@ __global__ __launch_bounds__(64, 4) void k_hv_walk(KParams p, const double * __r
 		{
 			const double v[5] = { oW, oT, oR, oU, oV };
 			const int slab[5] = { TMX_SLAB_W(L, kk), TMX_SLAB_T(L, kk), TMX_SLAB_R(L, kk), TMX_SLAB_U(L, kk), TMX_SLAB_V(L, kk) };
-			seam_store<5, RL>(p, &s[0], lane, here ? sdst : -1, sred, v, xout, slab, actn ? 5 : 1);
+			seam_store<5>(p, &s[0], lane, here ? sdst : -1, sred, v, xout, slab, actn ? 5 : 1);
 		}
 		wave_sync();
 	};
