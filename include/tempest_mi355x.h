@@ -433,10 +433,16 @@ enum {
 	                                 stored, 3 node-unique layout, 4 V.StepExplicit fused in, 5 uniform diffusion applied in the walk */
 	TMX_INFO_HYPERVIS_KERNEL,     /* the kernel of the last hyperviscosity pass: 0 the level-parallel one, n > 0 the walk with n segments per column (after the clamp
 	                                 to (levels + 1) / 2), -1 none yet */
-	TMX_INFO_PHYSICS_KERNEL       /* the kernel of the last tmx_physics_kessler / tmx_physics_dcmip2016 launch, -1 none yet, otherwise family | pbl << 2 | prec << 3 |
+	TMX_INFO_PHYSICS_KERNEL,      /* the kernel of the last tmx_physics_kessler / tmx_physics_dcmip2016 launch, -1 none yet, otherwise family | pbl << 2 | prec << 3 |
 	                                 n << 4; family (bits 0-1): 1 k_kessler (one lane per column; n = 0), 2 k_kessler_tile (n = kt, the wavefronts the levels
 	                                 of a column are dealt out to), 3 k_dcmip (pbl, prec the instantiation's; n = the bytes of dynamic LDS it was launched
 	                                 with, 0 the variant with its Thomas coefficients in HBM, whatever "dcmip_lds" asked for); pbl = prec = 0 for Kessler */
+	TMX_INFO_TRACER_COLUMN_KERNEL,/* the implicit tracer column kernel (k_vi_tracers_rows) of the last launch, -1 none yet, otherwise row lanes per column | log2 of the
+	                                 columns per workgroup << 8 | (1: every stored column, ARK232's form; 0: the unique columns behind V.StepImplicit) << 16 */
+	TMX_INFO_VERTICAL_KERNELS     /* the last launches of the three explicit-mode vertical kernels, -1 none of them yet, otherwise 12 bits each: V.StepExplicit's U,V
+	                                 update | the fully explicit tracer update << 12 | the explicitly evaluated implicit terms << 24; per kernel 0 the level-parallel
+	                                 (tracers: LDS-tiled) kernel, n the column walk with n segments, 0x800 | columns per workgroup the tracers' one-lane-per-column
+	                                 kernel (option "vt_column"), 0xfff that kernel not launched yet */
 };
 long long tmx_info(tmx_engine * e, int what);
 
@@ -553,6 +559,21 @@ int tmx_debug_program_prefix(int scheme, int first_step, int last_step, int * pa
  * column of `rows` rows is walked in on a grid of `ntiles` 64-column tiles.  option -n = n segments; -1000 = segments in pairs until the grid
  * has target_wavefronts wavefronts (4096 for vx_walk, 2048 for the other two), at least five rows each.  Always 1 .. rows. */
 int tmx_debug_walk_segments(int option, int ntiles, int rows, int target_wavefronts);
+/* Host logic of the vertical launchers, no device: the kernel shape a launcher picks at `levels` levels.  Every shape either asks for at most the
+ * 160 KB of LDS a CU has or does not fit; an ABI call whose launcher does not fit returns TMX_ERR_UNSUPPORTED before its first kernel, so the
+ * instances it names are untouched.  e == NULL: from the plain integers args[0 .. nargs) (missing ones take the engine's defaults);
+ * e != NULL (a finalized engine, plan-only ones included): the engine's own level count, sizes and options, and where it does not fit the
+ * return value and tmx_last_error are those of the refused ABI call.  Returns 0 fits, 1 does not fit, < 0 error.  out[2] = bytes of dynamic
+ * LDS, out[3] = where it does not fit, the largest level count that does (0: none).
+ *   launcher 0  column solve (tmxk_vi_fused).  args: unique columns, columns per wavefront (64), closed-form metric (1), stream columns of the
+ *               scratch (unbounded), vi_group (-1), vi_group_max (6400), vi_pair_workgroup (0), vi_producers (0), vi_ring_depth (0).
+ *               out[0] = TMX_INFO_COLUMN_KERNEL, out[1] = TMX_INFO_COLUMN_VARIANT of the launch (out[0] = -1: does not fit)
+ *   launcher 1  implicit tracer column update (launch_vt_solve).  args: all columns (0), vt_rows (1), vt_row_lanes (0), vt_lw8 (-1), vt_lanes (16).
+ *               out[0] = row lanes (0: does not fit), out[1] = log2 of the columns per workgroup
+ *   launcher 2, 3, 4  V.StepExplicit's U,V update, the fully explicit tracer update, the explicitly evaluated implicit terms.  args: the walk
+ *               option (-1000), 64-column tiles (1), U,V fused in (0; launcher 4).  out[0] = segments of the walk, 0 = level-parallel / LDS-tiled kernel
+ *   launcher 5  the one-lane-per-column tracer kernel of the fully explicit mode ("vt_column").  out[0] = columns per workgroup (0: does not fit) */
+int tmx_debug_vertical_shape(tmx_engine * e, int launcher, int levels, const int * args, int nargs, long long out[4]);
 /* Diagnostic builds of the library (-DTMX_H_TIMING) only, zeros otherwise: shader cycles per wavefront of the fused explicit kernel by
  * phase, out[16 instantiations (combination terms)][7 phases + wavefront count] (tools/h_timing.py); the read clears the counters. */
 int tmx_debug_h_timing(tmx_engine * e, unsigned long long * out);

@@ -252,7 +252,7 @@ __device__ __forceinline__ double exner_from_rhotheta(const KParams & p, double 
 // exp; tmx_rm_tables_to_lds fills it).  From global memory the two dependent table gathers of every evaluation are
 // vector-memory loads: in the column kernels each one cost an s_waitcnt vmcnt(0), i.e. a wait for the level prefetches
 // (and U-row stores) in flight as well.
-#define TMX_RMTAB_DOUBLES 512
+// (TMX_RMTAB_DOUBLES = 512: tmx_internal.h, beside the launchers' LDS sizes)
 __device__ __forceinline__ void tmx_rm_tables_to_lds(double * rmtab, int tid, int nthreads) {
 	for (int t = tid; t < 256; t += nthreads) {
 		rmtab[t] = tmx_rm_log_tab[t];

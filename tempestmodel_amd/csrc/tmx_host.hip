@@ -987,6 +987,12 @@ extern "C" long long tmx_info(tmx_engine * e, int what) {
 		case TMX_INFO_STAGE_KERNEL: return e->stage_kernel_launched;
 		case TMX_INFO_HYPERVIS_KERNEL: return e->hypervis_kernel_launched;
 		case TMX_INFO_PHYSICS_KERNEL: return e->physics_kernel_launched;
+		case TMX_INFO_TRACER_COLUMN_KERNEL: return e->vt_kernel_launched;
+		case TMX_INFO_VERTICAL_KERNELS: {      // 12 bits per kernel, 0xfff: that one not launched yet
+			const int * v = e->vwalk_launched;
+			if (v[0] < 0 && v[1] < 0 && v[2] < 0) return -1;
+			return (long long)(v[0] & 0xfff) | (long long)(v[1] & 0xfff) << 12 | (long long)(v[2] & 0xfff) << 24;
+		}
 		case TMX_INFO_COMM_RANKS: {      // what RCCL itself reports for the communicator (0: no communicator)
 			int n = 0;
 			if (e->comm && g_nccl.CommCount && g_nccl.CommCount(e->comm, &n) == 0) return n;
@@ -1016,6 +1022,80 @@ extern "C" int tmx_debug_h_walk_timing(tmx_engine * e, unsigned long long * out)
 // Host logic of the column walks, no device: the number of segments their launchers choose (walk_segments, tmx_internal.h)
 extern "C" int tmx_debug_walk_segments(int option, int ntiles, int rows, int target_wavefronts) {
 	return walk_segments(option, ntiles, rows, target_wavefronts);
+}
+
+// Would the launchers an ABI call is about to use fit?  Asked before the call's first kernel, so that a refused call leaves every instance as
+// it was.  (Needs no device: the shape functions of tmx_internal.h on the engine's own numbers.)
+int tmx_vertical_fit(tmx_engine * e, unsigned what) {
+	if (e->sw) return TMX_OK;
+	if ((what & TMX_FIT_VI) && e->nunique > 0) {
+		const ViShape s = vi_shape(e->L, vi_shape_in(e, e->metric_closed));
+		REQUIRE(s.fits(), TMX_ERR_UNSUPPORTED, "column solve (k_vi_pair): %d levels do not fit the LDS of a CU; this configuration serves up to %d levels", e->L, s.max_L);
+	}
+	if ((what & TMX_FIT_VT) && e->nt > 0 && e->nunique > 0) {
+		const VtShape s = vt_solve_shape(e, false);
+		REQUIRE(s.fits(), TMX_ERR_UNSUPPORTED, "tracer column update (k_vi_tracers_rows): %d levels do not fit the LDS of a CU; this configuration serves up to %d levels", e->L, s.max_L);
+	}
+	if ((what & TMX_FIT_VT_ALL) && e->nt > 0 && e->ncol > 0) {
+		const VtShape s = vt_solve_shape(e, true);
+		REQUIRE(s.fits(), TMX_ERR_UNSUPPORTED, "tracer column update (k_vi_tracers_rows): %d levels do not fit the LDS of a CU; this configuration serves up to %d levels", e->L, s.max_L);
+	}
+	if ((what & TMX_FIT_VT_EXPLICIT) && e->nt > 0 && e->ncol > 0 && e->opt_vt_column) {
+		const VtColumnShape s = vt_column_shape(e->L);
+		REQUIRE(s.fits(), TMX_ERR_UNSUPPORTED, "tracer column update (k_v_tracers_explicit_column, option vt_column): %d levels do not fit the LDS of a CU; this configuration serves up to %d levels",
+			e->L, s.max_L);
+	}
+	return TMX_OK;
+}
+// what a whole step may launch (tmx_step): implicit mode the column solve and both forms of the tracer update, fully explicit mode the tracer kernel
+unsigned tmx_vertical_fit_of_step(const tmx_engine * e) { return e->fully_explicit ? TMX_FIT_VT_EXPLICIT : (TMX_FIT_VI | TMX_FIT_VT | TMX_FIT_VT_ALL); }
+
+// Host logic of the vertical launchers, no device (tmx_internal.h: vi_shape, vt_solve_shape, vwalk_shape, vt_column_shape)
+extern "C" int tmx_debug_vertical_shape(tmx_engine * e, int launcher, int levels, const int * args, int nargs, long long out[4]) {
+	REQUIRE(out && (e || levels >= 1) && (nargs == 0 || args), TMX_ERR_INVALID, "tmx_debug_vertical_shape: bad argument");
+	auto arg = [&](int i, int dflt) { return i < nargs ? args[i] : dflt; };
+	out[0] = out[1] = out[2] = out[3] = 0;
+	if (e) {
+		REQUIRE(e->finalized && launcher >= 0 && launcher <= 5, TMX_ERR_INVALID, "tmx_debug_vertical_shape: engine not finalized or unknown launcher %d", launcher);
+		static const unsigned bit[6] = { TMX_FIT_VI, TMX_FIT_VT, 0, 0, 0, TMX_FIT_VT_EXPLICIT };
+		const unsigned what = (launcher == 1 && arg(0, 0)) ? TMX_FIT_VT_ALL : bit[launcher];
+		const int r = tmx_vertical_fit(e, what);
+		levels = e->L;
+		if (r) {      // the message is set; out[3]: the limit it names
+			out[0] = -1;
+			out[3] = launcher == 0 ? vi_shape(levels, vi_shape_in(e, e->metric_closed)).max_L : (launcher == 1 ? vt_solve_shape(e, arg(0, 0) != 0).max_L : vt_column_shape(levels).max_L);
+			return r;
+		}
+	}
+	switch (launcher) {
+		case 0: {      // column solve: args = unique columns, columns per wavefront, closed-form metric, stream columns, vi_group, vi_group_max, vi_pair_workgroup, vi_producers, vi_ring_depth
+			const ViShapeIn in = e ? vi_shape_in(e, e->metric_closed)
+				: ViShapeIn{ arg(0, 0), arg(1, 64), arg(2, 1), arg(3, 1 << 30), arg(4, -1), arg(5, 6400), arg(6, 0), arg(7, 0), arg(8, 0), 1, 0 };
+			REQUIRE(in.nunique >= 1 && in.cpw >= 1 && in.cpw <= 64, TMX_ERR_INVALID, "tmx_debug_vertical_shape: bad column-solve arguments");
+			const ViShape s = vi_shape(levels, in);
+			out[0] = s.kernel; out[1] = s.fits() ? (s.kernel == 1 ? (s.pairs | s.producers << 4 | s.ring << 8) : 0) : 0; out[2] = (long long)s.bytes; out[3] = s.max_L;
+			return s.fits() ? 0 : 1;
+		}
+		case 1: {      // tracer column update: args = all columns, vt_rows, vt_row_lanes, vt_lw8, vt_lanes
+			const bool all = arg(0, 0) != 0;
+			const VtShape s = e ? vt_solve_shape(e, all) : vt_solve_shape(levels, arg(1, 1), arg(2, 0), arg(3, -1), all ? 64 : arg(4, 16));
+			out[0] = s.nr; out[1] = s.lwb; out[2] = (long long)s.bytes; out[3] = s.max_L;
+			return s.fits() ? 0 : 1;
+		}
+		case 2: case 3: case 4: {      // the walks of V.StepExplicit (U,V), of the explicit tracer update, of the explicitly evaluated implicit terms: args = option, tiles, with U,V
+			const int which = launcher - 2;
+			const int opt = e ? (which == TMX_WALK_VX ? e->opt_vx_walk : (which == TMX_WALK_VT ? e->opt_vt_walk : e->opt_vite_walk)) : arg(0, -1000);
+			const WalkShape s = vwalk_shape(which, levels, opt, e ? (e->ncol + 63) / 64 : arg(1, 1), arg(2, 0) != 0);
+			out[0] = s.nseg; out[2] = (long long)s.bytes;
+			return 0;
+		}
+		case 5: {      // option "vt_column"
+			const VtColumnShape s = vt_column_shape(levels);
+			out[0] = s.lw; out[2] = (long long)s.bytes; out[3] = s.max_L;
+			return s.fits() ? 0 : 1;
+		}
+	}
+	REQUIRE(false, TMX_ERR_INVALID, "tmx_debug_vertical_shape: unknown launcher %d", launcher);
 }
 
 // Statistics of the two-wavefront column kernel: how many pivot steps found the same pivot row in all 64 columns of a

@@ -336,6 +336,8 @@ struct tmx_engine {
 	bool vi_unique = false;                  // transient: the column solve runs on the unique slabs (tmxk_vi_fused)
 	ProfSlot prof_slots[TMX_K_COUNT];
 	std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> prof_pending;
+	int vt_kernel_launched = -1;             // the implicit tracer column kernel of the last launch (TMX_INFO_TRACER_COLUMN_KERNEL): row lanes | log2 columns << 8 | all columns << 16; -1 none yet
+	int vwalk_launched[3] = { -1, -1, -1 };  // the explicit-mode vertical kernels' last launches (TMX_INFO_VERTICAL_KERNELS; TMX_WALK_VX / _VT / _VITE): 0 level-parallel, n segments, 0x800 | columns "vt_column"; -1 none yet
 };
 
 void tmx_set_error(const char * fmt, ...);
@@ -444,6 +446,134 @@ static inline int walk_segments(int option, int ntiles, int rows, int target_wav
 	if (option == -1000) for (nseg = 2; ntiles * nseg < target_wavefronts && rows / (nseg + 2) >= 5; nseg += 2) { }
 	return nseg < 1 ? 1 : (nseg > rows ? rows : nseg);
 }
+
+// ---- The kernel shape every launcher of the vertical family picks from the level count: host-only functions of plain integers, so that the
+// CPU tests reach them without a device (tmx_debug_vertical_shape).  A launcher calls its function and launches what comes back; a shape
+// either needs at most TMX_CU_LDS bytes of dynamic LDS or does not fit (fits() false): then the ABI call refuses (TMX_ERR_UNSUPPORTED) before
+// its first kernel, naming max_L, the largest level count the kernel serves in that configuration.
+#define TMX_CU_LDS ((size_t)160 * 1024)      // LDS of a CU (gfx950)
+#define TMX_RMTAB_DOUBLES 512                // exp / log tables of tmx_refmath.h in LDS (tmx_device.h: tmx_rm_tables_to_lds)
+#define TMX_RING_NQ 20                       // doubles per column of a block row in k_vi_pair's ring (tmx_k_column.hip: TMX_RSLOT)
+#ifndef TMX_RING_DEPTH
+#define TMX_RING_DEPTH 3                     // block rows of that ring (4 with two assembly wavefronts)
+#endif
+#define TMX_GROUP_RING_DOUBLES (16 * (3 * TMX_BW + 3))      // k_vi_group: ring of 16 block rows per column, which also receives the 3 (L + 1) solution entries
+// the largest level count below L at which fits(l) holds (every fit test here is monotone in L); 0: none
+template <class F> static inline int largest_level_that_fits(int L, F fits) { for (int l = L - 1; l >= 3; l--) if (fits(l)) return l; return 0; }
+
+// The implicit column solve (tmxk_vi_fused).  kernel: 2 lane group (no dynamic LDS; its ring holds the solution up to 159 levels), 1 the
+// two-role pair kernel with `pairs` column groups per workgroup, `producers` assembly wavefronts per pair and a ring of `ring` block rows,
+// 0 the one-wavefront kernel of the experiments flavour; -1 nothing fits.
+struct ViShape { int kernel, pairs, producers, ring; size_t bytes; int max_L; bool fits() const { return kernel >= 0; } };
+struct ViShapeIn { int nunique, cpw, closed, stream_cols, group, group_max, pair_wg, producers, ring_depth, use_pair, default_ring; };
+static inline size_t vi_pair_lds(int L, int pairs, int ring) {
+	const size_t common = walk_lds_bytes(L, TMX_RMTAB_DOUBLES);      // operator tables, 1 - eta, exp / log tables
+	return common + pairs * ((size_t)ring * TMX_RING_NQ * 64 * sizeof(double) + (size_t)TMX_FTOT * (L + 1) * sizeof(int) + 4 * sizeof(int));      // ring, fill-in masks, hand-over counters
+}
+static inline ViShape vi_shape_at(int L, const ViShapeIn & in) {
+	ViShape s = { -1, 0, 0, 0, 0, 0 };
+	// the lane-group kernel streams 16 doubles per row and column (the scratch is sized for the pair kernel's 10) and keeps the solution in
+	// its ring: launched only where both fit -- otherwise the pair kernel serves the share
+	const bool group_fits = (size_t)((in.nunique + 3) / 4) * 64 <= (size_t)(TMX_BW + 1) * in.stream_cols && TMX_FTOT * (L + 1) <= TMX_GROUP_RING_DOUBLES;
+	if (group_fits && (in.group == 1 || (in.group < 0 && in.nunique <= in.group_max))) { s.kernel = 2; return s; }
+	if (!in.use_pair) {
+		s.bytes = walk_lds_bytes(L) + (size_t)TMX_FTOT * (L + 1) * sizeof(int);
+		if (s.bytes <= TMX_CU_LDS) s.kernel = 0;
+		return s;
+	}
+	const int cpw = in.cpw, ngrp = (in.nunique + cpw - 1) / cpw;
+	int pairs = (in.pair_wg > 0) ? in.pair_wg : ((ngrp <= 256) ? 1 : 2);
+	// two assembly wavefronts per column group where every wavefront still has a SIMD to itself (option "vi_producers": 0 auto, 1, 2)
+	bool two_prod = in.closed && pairs == 1 && cpw == 64 && (in.producers == 2 || (in.producers == 0 && ngrp * 3 <= 1024));
+	for (;;) {
+		int ring;
+		if (two_prod) ring = TMX_RING_DEPTH + 1;      // two rows are being written at a time: the ring holds one more
+		else {
+			// three block rows, or two where only that lets a second workgroup onto every CU (option "vi_ring_depth": 0 auto, 2, 3) ...
+			ring = TMX_RING_DEPTH;
+			if (in.ring_depth == 2 || in.ring_depth == 3) ring = in.ring_depth;
+			else if (2 * vi_pair_lds(L, pairs, 3) > TMX_CU_LDS && 2 * vi_pair_lds(L, pairs, 2) <= TMX_CU_LDS) ring = 2;
+			if (in.default_ring) ring = TMX_RING_DEPTH;      // (the separate-back-substitution cross-check is instantiated with the default depth)
+			// ... or where three do not fit one workgroup
+			else if (ring == 3 && vi_pair_lds(L, pairs, 3) > TMX_CU_LDS) ring = 2;
+		}
+		s.bytes = vi_pair_lds(L, pairs, ring);
+		if (s.bytes <= TMX_CU_LDS) { s.kernel = 1; s.pairs = pairs; s.producers = two_prod ? 2 : 1; s.ring = ring; return s; }
+		// a smaller shape of the same kernel: one assembly wavefront, then one pair per workgroup
+		if (two_prod) two_prod = false; else if (pairs > 1) pairs = 1; else return s;
+	}
+}
+static inline ViShape vi_shape(int L, const ViShapeIn & in) {
+	ViShape s = vi_shape_at(L, in);
+	if (!s.fits()) s.max_L = largest_level_that_fits(L, [&](int l) { return vi_shape_at(l, in).fits(); });
+	return s;
+}
+static inline ViShapeIn vi_shape_in(const tmx_engine * e, bool closed) {
+	return { e->nunique, ((!TMX_EXP || e->vi_pair == 1 || (e->vi_pair < 0 && e->vi_carry)) ? e->vi_cpw : 64), closed ? 1 : 0, e->vi_stream_cols, e->vi_group, e->vi_group_max,
+		e->vi_pair_wg, e->vi_producers, e->vi_ring_depth, (!TMX_EXP || e->vi_pair == 1 || (e->vi_pair < 0 && e->vi_carry)) ? 1 : 0, (TMX_EXP && e->vi_split_back != 0) ? 1 : 0 };
+}
+
+// The implicit column update of the tracers (launch_vt_solve): nr row lanes per column, 1 << lwb columns per workgroup; nr = 0: nothing fits.
+// LDS of k_vi_tracers_rows per workgroup of lw columns: band matrix A [L][4], right-hand side F and tracer column qn [L] each, xi_dot initial /
+// updated and the velocity jump on the interfaces [L + 1] each: (9L + 3) x lw doubles
+struct VtShape { int nr, lwb; size_t bytes; int max_L; bool fits() const { return nr > 0; } };
+static inline size_t vt_solve_lds(int L, int lw) { return ((size_t)L * 4 + (size_t)L * 2 + (size_t)(L + 1) * 3) * lw * sizeof(double); }
+static inline VtShape vt_solve_shape_at(int L, int opt_rows, int opt_nr, int opt_lw8, int lanes) {
+	VtShape s = { 0, 0, 0, 0 };
+	int nr, lwb;
+	if (opt_rows && vt_solve_lds(L, 16) <= TMX_CU_LDS) {
+		lwb = (opt_lw8 >= 0 ? opt_lw8 == 1 : L <= 48) ? 3 : 4;      // ne30, 2 tracers: L30 1.308 (8 columns) / 1.358 (16) ms per step, L60 3.35 / 3.21
+		nr = opt_nr ? opt_nr : (L > 48 ? 32 : 16);                  // measured at ne30: L30 1.36 (16) / 1.49 (32) ms, L60 3.50 (16) / 3.25 (32) ms per step
+		if (nr == 4 && lwb == 3) nr = 16;                           // (no instance of 4 row lanes x 8 columns: less than a wavefront)
+	} else {
+		nr = 1;
+		lwb = (lanes == 8) ? 3 : ((lanes == 16) ? 4 : ((lanes == 32) ? 5 : 6));
+		while (lwb > 3 && vt_solve_lds(L, 1 << lwb) > TMX_CU_LDS) lwb--;
+	}
+	s.bytes = vt_solve_lds(L, 1 << lwb);
+	if (s.bytes <= TMX_CU_LDS) { s.nr = nr; s.lwb = lwb; }
+	return s;
+}
+static inline VtShape vt_solve_shape(int L, int opt_rows, int opt_nr, int opt_lw8, int lanes) {
+	VtShape s = vt_solve_shape_at(L, opt_rows, opt_nr, opt_lw8, lanes);
+	if (!s.fits()) s.max_L = largest_level_that_fits(L, [&](int l) { return vt_solve_shape_at(l, opt_rows, opt_nr, opt_lw8, lanes).fits(); });
+	return s;
+}
+// the unique columns behind V.StepImplicit (option "vt_lanes", default 16) / every stored column at the end of StepImplicitTermsExplicitly (64)
+static inline VtShape vt_solve_shape(const tmx_engine * e, bool all_columns) {
+	return vt_solve_shape(e->L, e->opt_vt_rows, e->opt_vt_nr, e->opt_vt_lw8, all_columns ? 64 : e->opt_vt_lanes);
+}
+
+// The three column walks of the explicit-mode vertical kernels (k_v_explicit_slide, k_v_tracers_explicit_slide, k_vi_terms_explicit_slide): the
+// walk with nseg segments where the option asks for one (< 0) and its tables fit 64 KB of LDS, else nseg = 0: the level-parallel (for the
+// tracers: LDS-tiled) kernel, which takes no dynamic LDS and any level count.
+struct WalkShape { int nseg; size_t bytes; };
+enum { TMX_WALK_VX = 0, TMX_WALK_VT = 1, TMX_WALK_VITE = 2 };
+static inline WalkShape vwalk_shape(int which, int L, int option, int ntiles, bool with_uv = false) {
+	const size_t b = walk_lds_bytes(L, which == TMX_WALK_VITE ? TMX_RMTAB_DOUBLES : 0);
+	if (option < 0 && !(which == TMX_WALK_VITE && with_uv) && b <= 64 * 1024)
+		return { walk_segments(option, ntiles, which == TMX_WALK_VITE ? L + 1 : L, which == TMX_WALK_VX ? 4096 : 2048), b };
+	return { 0, 0 };
+}
+
+// The one-lane-per-column tracer kernel of the fully explicit mode (option "vt_column"): 64 columns per workgroup, or 32 where only they fit a
+// CU; lw = 0: neither does.  LDS per workgroup of lw columns: xd0 and rhoe on the interfaces [L + 1] each, qn and mixr on the levels [L] each:
+// (4L + 2) x lw doubles
+struct VtColumnShape { int lw; size_t bytes; int max_L; bool fits() const { return lw > 0; } };
+static inline size_t vt_explicit_column_lds(int L, int lw) { return ((size_t)(L + 1) * 2 + (size_t)L * 2) * lw * sizeof(double); }
+static inline VtColumnShape vt_column_shape(int L) {
+	VtColumnShape s = { 0, 0, 0 };
+	const int lw = (vt_explicit_column_lds(L, 64) <= TMX_CU_LDS) ? 64 : 32;
+	s.bytes = vt_explicit_column_lds(L, lw);
+	if (s.bytes <= TMX_CU_LDS) s.lw = lw;
+	else s.max_L = largest_level_that_fits(L, [](int l) { return vt_explicit_column_lds(l, 32) <= TMX_CU_LDS; });
+	return s;
+}
+// Refusal of an ABI call before its first kernel: TMX_OK, or TMX_ERR_UNSUPPORTED with the message set.  what: bit 0 the column solve, 1 the
+// tracers behind it (unique columns), 2 the tracers' all-columns form, 3 the explicit mode's tracer kernel
+enum { TMX_FIT_VI = 1, TMX_FIT_VT = 2, TMX_FIT_VT_ALL = 4, TMX_FIT_VT_EXPLICIT = 8 };
+int tmx_vertical_fit(tmx_engine * e, unsigned what);
+unsigned tmx_vertical_fit_of_step(const tmx_engine * e);
 void tmxk_dss(tmx_engine * e, const KParams & p, double * x, int g0, int g1);
 void tmxk_hypervis(tmx_engine * e, const KParams & p, const double * xsrc, const double * xbase, double * xout,
 	double dt, double nu_s, double nu_d, double nu_v, int scale_locally, bool pull_dss = false);

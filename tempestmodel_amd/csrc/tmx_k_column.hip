@@ -491,7 +491,7 @@ __device__ __forceinline__ void lu_store_urow(const double (&piv)[TMX_BW], doubl
 // 27 entries, plus the three residuals: 20 doubles per column instead of 30.  A third fewer LDS writes and reads per block row,
 // and room for a THREE-deep ring in the LDS that held two dense block rows (TMX_RING_DEPTH).  TMX_RSLOT[kind][d] = slot of band
 // entry d of the row of that kind, -1 = structural zero (the consumer takes the literal 0.0 the dense ring carried).
-#define TMX_RING_NQ 20
+// (TMX_RING_NQ = 20: tmx_internal.h, beside the launchers' LDS sizes)
 __device__ constexpr int TMX_RSLOT[3][TMX_BW] = {
 	{ -1, 0, -1, -1, 1, 2, -1, 3, 4 },          // rho*theta row
 	{ 5, 6, 7, 8, 9, 10, -1, 11, -1 },          // W row
@@ -861,9 +861,7 @@ __global__ __launch_bounds__(64) void k_vi_fused(KParams p, const double * xin, 
 // BACK = false: the kernel ends with the elimination and leaves the fill-in masks of its U rows in `gmask` ([column group][3(L+1)]);
 // k_vi_back does the back substitution as a launch of its own (one wavefront per workgroup, so that the HBM-bound half of the
 // solve is spread evenly over the CUs whatever the residency of the pairs was).
-#ifndef TMX_RING_DEPTH
-#define TMX_RING_DEPTH 3
-#endif
+// (TMX_RING_DEPTH, default 3: tmx_internal.h, beside the launchers' LDS sizes)
 // (the counters are accessed through explicit LDS pointers: a volatile access through a generic pointer compiles to a FLAT load followed
 // by s_waitcnt vmcnt(0), i.e. a wait for every U-row store in flight)
 typedef __attribute__((address_space(3))) int tmx_lds_int;
@@ -1446,8 +1444,8 @@ void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double
 	if (e->nunique == 0) return;
 	// node-unique layout (e->vi_unique, set by the caller together with tmxu_params_columns): unique column u IS state column u, no in-patch copies to fill
 	const int * ucolp = e->vi_unique ? nullptr : (const int *)e->d_ucol, * udepp = e->vi_unique ? nullptr : (const int *)e->d_udep;
-	const size_t lds = (size_t)TMX_OP_COUNT * (p.L + 1) * TMX_OPW * sizeof(double) + (size_t)(2 * p.L + 1) * sizeof(double) + (size_t)TMX_FTOT * (p.L + 1) * sizeof(int);
 	const bool sparse = e->opt_vi_sparse != 0;      // A/B switch (option "vi_sparse"), default on
+	// The kernel and its shape: vi_shape (tmx_internal.h), a host function of the level count, the column count and the options.
 	// The pair kernel shortens the per-column dependent chain to max(assembly, elimination) and is built for two
 	// wavefronts per SIMD (256 registers): the 1024 SIMDs hold 1024 pairs at once.  Measured per launch: ne30 on one
 	// GPU (760 column groups) 197-211 us against 229 us for the one-wavefront kernel; ne60 (3038 groups, three rounds)
@@ -1456,33 +1454,29 @@ void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double
 	// size; the one-wavefront kernel stays as TMX_VI_PAIR=0 (bit-identical, tested).
 	// few columns for the chip (strong-scaling share): one column per 16-lane group
 	// (the options that select it may be set after tmx_finalize sized the scratch for the pair kernel's 10 doubles per row and column: the
-	// lane-group kernel streams 16, and is only launched where its stream fits -- otherwise the pair kernel serves the share)
-	const bool group_fits = (size_t)((e->nunique + 3) / 4) * 64 <= (size_t)TMX_UW * e->vi_stream_cols;
-	if (group_fits && (e->vi_group == 1 || (e->vi_group < 0 && e->nunique <= e->vi_group_max))) {
+	// lane-group kernel streams 16, and is only launched where its stream fits and its ring holds the solution -- otherwise the pair kernel serves the share)
+	const ViShape shape = vi_shape_at(p.L, vi_shape_in(e, p.closed != 0));
+	if (!shape.fits()) return;      // (every caller has asked tmx_vertical_fit before its first kernel: not reached)
+	if (shape.kernel == 2) {
 		const int nwg = (e->nunique + 3) / 4;
 		e->vi_kernel_launched = 2; e->vi_variant_launched = 0;
 		if (p.closed) hipLaunchKernelGGL((k_vi_group<true>), dim3(nwg), dim3(64), 0, e->stream, p, xin, xup, dt, e->nunique, ucolp, udepp, e->d_ab, e->d_flag);
 		else hipLaunchKernelGGL((k_vi_group<false>), dim3(nwg), dim3(64), 0, e->stream, p, xin, xup, dt, e->nunique, ucolp, udepp, e->d_ab, e->d_flag);
 		return;
 	}
+	const size_t lds = shape.bytes;
 	const bool use_pair = !TMX_EXP || (e->vi_pair == 1) || (e->vi_pair < 0 && e->vi_carry);
 	e->vi_kernel_launched = use_pair ? 1 : 0;      // (tmx_info(TMX_INFO_COLUMN_KERNEL): which kernel really ran, whatever the options asked for)
 	e->vi_variant_launched = 0;
 	const int cpw = use_pair ? e->vi_cpw : 64;
 	const int ngrp = (e->nunique + cpw - 1) / cpw;
 	if (use_pair) {
-		const size_t lds_common = (size_t)TMX_OP_COUNT * (p.L + 1) * TMX_OPW * sizeof(double) + (size_t)(2 * p.L + 1) * sizeof(double) + TMX_RMTAB_DOUBLES * sizeof(double);
-		const int pairs = (e->vi_pair_wg > 0) ? e->vi_pair_wg : ((ngrp <= 256) ? 1 : 2);
-		// two assembly wavefronts per column group where every wavefront still has a SIMD to itself (option "vi_producers": 0 auto, 1, 2)
-		const bool two_prod = p.closed && pairs == 1 && cpw == 64 && (e->vi_producers == 2 || (e->vi_producers == 0 && ngrp * 3 <= 1024));
-		auto lds_pair_of = [&](int depth) { return (size_t)depth * TMX_RING_NQ * 64 * sizeof(double) + (size_t)TMX_FTOT * (p.L + 1) * sizeof(int) + 4 * sizeof(int); };      // ring, fill-in masks, hand-over counters
-		// ring depth: three block rows, or two where only that lets a second workgroup onto every CU (160 KB of LDS; option "vi_ring_depth": 0 auto, 2, 3)
-		const size_t cu_lds = 160 * 1024;
-		int rdt = TMX_RING_DEPTH;
-		if (e->vi_ring_depth == 2 || e->vi_ring_depth == 3) rdt = e->vi_ring_depth;
-		else if (!two_prod && 2 * (lds_common + pairs * lds_pair_of(3)) > cu_lds && 2 * (lds_common + pairs * lds_pair_of(2)) <= cu_lds) rdt = 2;
-		if (TMX_EXP && e->vi_split_back != 0) rdt = TMX_RING_DEPTH;      // (the separate-back-substitution cross-check is instantiated with the default depth)
-		const size_t lds_pair = lds_pair_of(two_prod ? TMX_RING_DEPTH + 1 : rdt);
+		// pairs per workgroup (option "vi_pair_workgroup": 0 auto -- 1 up to 256 column groups, else 2), assembly wavefronts per column group (option
+		// "vi_producers": 0 auto, 1, 2), block rows of the ring (three, or two where only that lets a second workgroup onto every CU or where three do
+		// not fit one; option "vi_ring_depth": 0 auto, 2, 3) and the bytes of dynamic LDS they take, at most the 160 KB of a CU: vi_shape_at
+		const int pairs = shape.pairs, rdt = shape.ring;
+		const bool two_prod = shape.producers == 2;
+		const size_t lds_wg = shape.bytes;
 		// back substitution as a launch of its own (TMX_VI_SPLIT_BACK=0: inside the pair kernel); the masks go through d_rhs,
 		// which only the split cross-check kernels use otherwise
 		const bool split_back = TMX_EXP && e->vi_split_back != 0;      // (experiments flavour only)
@@ -1491,15 +1485,15 @@ void tmxk_vi_fused(tmx_engine * e, const KParams & p, const double * xin, double
 		const bool split = split_back && (size_t)ngrp_launched * TMX_FTOT * (p.L + 1) * sizeof(int) <= (size_t)TMX_FTOT * (p.L + 1) * e->NUS * sizeof(double);
 		// (tmx_info(TMX_INFO_COLUMN_VARIANT): pairs per workgroup, assembly wavefronts per pair and the RD of the instantiation launched below)
 		const bool two_launched = two_prod && !(TMX_EXP && split);
-		e->vi_variant_launched = pairs | (two_launched ? 2 : 1) << 4 | (two_launched ? TMX_RING_DEPTH + 1 : rdt) << 8;
-#define LAUNCH_PAIR(CL_, NP_) do { if (TMX_EXP && split) hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, TMX_EXP == 0>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_common + NP_ * lds_pair, \
+		e->vi_variant_launched = pairs | (two_launched ? 2 : 1) << 4 | (two_prod && !two_launched ? TMX_RING_DEPTH : rdt) << 8;
+#define LAUNCH_PAIR(CL_, NP_) do { if (TMX_EXP && split) hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, TMX_EXP == 0>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_wg, \
 			e->stream, p, xin, xup, dt, e->nunique, e->vi_stream_cols, ucolp, udepp, e->d_ab, e->d_rhs, e->d_flag, cpw, e->d_pivot_stats, (int *)e->d_rhs, 0); \
-		else if (rdt == 2) hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, true, 1, 2>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_common + NP_ * lds_pair, \
+		else if (rdt == 2) hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, true, 1, 2>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_wg, \
 			e->stream, p, xin, xup, dt, e->nunique, e->vi_stream_cols, ucolp, udepp, e->d_ab, e->d_rhs, e->d_flag, cpw, e->d_pivot_stats, (int *)nullptr, stagger); \
-		else hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, true, 1, 3>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_common + NP_ * lds_pair, \
+		else hipLaunchKernelGGL((k_vi_pair<true, CL_, NP_, true, 1, 3>), dim3((ngrp + NP_ - 1) / NP_), dim3(64, 2 * NP_), lds_wg, \
 			e->stream, p, xin, xup, dt, e->nunique, e->vi_stream_cols, ucolp, udepp, e->d_ab, e->d_rhs, e->d_flag, cpw, e->d_pivot_stats, (int *)nullptr, stagger); } while (0)
 		if (two_prod && !(TMX_EXP && split))
-			hipLaunchKernelGGL((k_vi_pair<true, true, 1, true, 2>), dim3(ngrp), dim3(64, 3), lds_common + lds_pair, e->stream, p, xin, xup, dt, e->nunique, e->vi_stream_cols,
+			hipLaunchKernelGGL((k_vi_pair<true, true, 1, true, 2>), dim3(ngrp), dim3(64, 3), lds_wg, e->stream, p, xin, xup, dt, e->nunique, e->vi_stream_cols,
 				ucolp, udepp, e->d_ab, e->d_rhs, e->d_flag, cpw, e->d_pivot_stats, (int *)nullptr, stagger);
 		else
 		if (pairs == 1) { if (p.closed) LAUNCH_PAIR(true, 1); else LAUNCH_PAIR(false, 1); }

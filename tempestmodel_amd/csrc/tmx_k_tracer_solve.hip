@@ -209,35 +209,23 @@ template <int NR, int LWB> __global__ __launch_bounds__(NR << LWB) void k_vi_tra
 // The columns a launch updates: all of them (ucol == nullptr), or the unique ones with up to three dependents each that receive a copy
 struct ColumnSet { int ncols; const int * ucol, * udep; };
 
-// LDS working set of k_vi_tracers_rows per workgroup of lw columns: band matrix A [L][4], right-hand side F and tracer column qn [L] each,
-// xi_dot initial / updated and the velocity jump (xd0, xd1, jmp) on the interfaces [L + 1] each: (9L + 3) x lw doubles
-static size_t vt_solve_lds(int L, int lw) { return ((size_t)L * 4 + (size_t)L * 2 + (size_t)(L + 1) * 3) * lw * sizeof(double); }
-
-// The implicit column update of the tracers on a set of columns.  Option "vt_rows" (default 1), where the 16-column working set fits the
+// The implicit column update of the tracers on a set of columns; the shape comes from vt_solve_shape_at (tmx_internal.h, with the LDS working set
+// vt_solve_lds).  Option "vt_rows" (default 1), where the 16-column working set fits the
 // 160 KB of a CU (L <= 141): NR row lanes per column -- 16 (four wavefronts per 16 columns) up to 48 levels, 32 above (option
 // "vt_row_lanes" = 4 | 8 | 16 | 32) -- and 8 columns per workgroup up to 48 levels (half the LDS per workgroup, twice the workgroups per
 // CU), 16 above (option "vt_lw8" = 0 | 1).  Fewer columns per workgroup = more workgroups per CU: the kernel lives in LDS (dependent
 // read-modify-write chains of ~100 cycles each), and with 16 columns per workgroup five wavefronts share a CU and hide each other's LDS
 // latency.  Else ("vt_rows" = 0, or too many levels): one row lane per column, `lanes` = 8 | 16 | 32 | 64 columns per workgroup,
 // reduced to the largest power of two whose working set fits a CU (64 up to L = 35, 32 up to 70, 16 up to 141, 8 up to 284).
-// Returns -1 where no shape fits.
+// Returns -1 where no shape fits (every caller has asked tmx_vertical_fit before its first kernel).
 static int launch_vt_solve(tmx_engine * e, const KParams & p, const ColumnSet & cs, const double * xin, const double * w0, const double * xbase, double * xup,
 	double dt, int lanes)
 {
-	const size_t cu_lds = 160 * 1024;
-	int nr, lwb;
-	if (e->opt_vt_rows && vt_solve_lds(p.L, 16) <= cu_lds) {
-		const int nr_env = e->opt_vt_nr, lw8_env = e->opt_vt_lw8;
-		lwb = (lw8_env >= 0 ? lw8_env == 1 : p.L <= 48) ? 3 : 4;      // ne30, 2 tracers: L30 1.308 (8 columns) / 1.358 (16) ms per step, L60 3.35 / 3.21
-		nr = nr_env ? nr_env : (p.L > 48 ? 32 : 16);                  // measured at ne30: L30 1.36 (16) / 1.49 (32) ms, L60 3.50 (16) / 3.25 (32) ms per step
-		if (nr == 4 && lwb == 3) nr = 16;                             // (no instance of 4 row lanes x 8 columns: less than a wavefront)
-	} else {
-		nr = 1;
-		lwb = (lanes == 8) ? 3 : ((lanes == 16) ? 4 : ((lanes == 32) ? 5 : 6));
-		while (lwb > 3 && vt_solve_lds(p.L, 1 << lwb) > cu_lds) lwb--;
-	}
-	const size_t lds = vt_solve_lds(p.L, 1 << lwb);
-	if (lds > cu_lds) return -1;
+	const VtShape shape = vt_solve_shape_at(p.L, e->opt_vt_rows, e->opt_vt_nr, e->opt_vt_lw8, lanes);
+	if (!shape.fits()) return -1;
+	const int nr = shape.nr, lwb = shape.lwb;
+	const size_t lds = shape.bytes;
+	e->vt_kernel_launched = nr | lwb << 8 | (cs.ucol ? 0 : 1) << 16;      // (tmx_info(TMX_INFO_TRACER_COLUMN_KERNEL))
 #define VT_SOLVE(NR_, LWB_) if (nr == NR_ && lwb == LWB_) { \
 		(void)hipFuncSetAttribute((const void *)k_vi_tracers_rows<NR_, LWB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
 		hipLaunchKernelGGL((k_vi_tracers_rows<NR_, LWB_>), dim3((cs.ncols + (1 << LWB_) - 1) >> LWB_), dim3(NR_ << LWB_), lds, e->stream, p, e->nt, xin, w0, xbase, xup, dt, \

@@ -120,11 +120,13 @@ __global__ __launch_bounds__(128) void k_v_explicit_slide(KParams p, const doubl
 
 void tmxk_v_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_udiff_uv) {
 	const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
-	const size_t lds_slide = walk_lds_bytes(p.L);
-	if (e->opt_vx_walk < 0 && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
+	const WalkShape shape = vwalk_shape(TMX_WALK_VX, p.L, e->opt_vx_walk, nt_);
+	e->vwalk_launched[TMX_WALK_VX] = shape.nseg;      // (tmx_info(TMX_INFO_VERTICAL_KERNELS): the walk's segments, 0 the level-parallel kernel below)
+	if (shape.nseg) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
 		// (a light kernel, four resident wavefronts per SIMD: ne30 L40 on one GPU 1 / 2 / 4 segments 3.84 / 3.76 / 3.75 ms per step of BASELINE config 4's
 		// shape, the level-parallel kernel 3.98)
-		const int nseg = walk_segments(e->opt_vx_walk, nt_, p.L, 4096);
+		const int nseg = shape.nseg;
+		const size_t lds_slide = shape.bytes;
 		dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
 		const double cf = with_udiff_uv ? e->cfg.uniform_diffusion_vector / (e->cfg.ztop * e->cfg.ztop) : 0.0;
 #define LAUNCH_VXS(UD_, CL_) hipLaunchKernelGGL((k_v_explicit_slide<UD_, CL_>), grd, blk, lds_slide, e->stream, p, xin, xup, dt, (const double *)(with_udiff_uv ? e->d_ref : nullptr), cf, nt_, xm, nseg)
@@ -202,15 +204,14 @@ __global__ __launch_bounds__(64) void k_v_tracers_explicit_column(KParams p, int
 	}
 }
 
-// LDS working set of k_v_tracers_explicit_column per workgroup of lw columns: xd0 and rhoe on the interfaces [L + 1] each, qn and mixr on
-// the levels [L] each: (4L + 2) x lw doubles
-static size_t vt_explicit_column_lds(int L, int lw) { return ((size_t)(L + 1) * 2 + (size_t)L * 2) * lw * sizeof(double); }
-
-// 64 columns per workgroup, or 32 where only they fit the 160 KB of a CU; returns -1 where neither does
+// 64 columns per workgroup, or 32 where only they fit the 160 KB of a CU (vt_column_shape, tmx_internal.h, with the LDS working set
+// vt_explicit_column_lds); returns -1 where neither does (every caller has asked tmx_vertical_fit before its first kernel)
 static int launch_vt_explicit_column(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) {
-	const int lw = (vt_explicit_column_lds(p.L, 64) <= 160 * 1024) ? 64 : 32;
-	const size_t lds = vt_explicit_column_lds(p.L, lw);
-	if (lds > 160 * 1024) return -1;
+	const VtColumnShape shape = vt_column_shape(p.L);
+	if (!shape.fits()) return -1;
+	const int lw = shape.lw;
+	const size_t lds = shape.bytes;
+	e->vwalk_launched[TMX_WALK_VT] = 0x800 | lw;      // (tmx_info(TMX_INFO_VERTICAL_KERNELS))
 	const double ks = e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0;
 #define LAUNCH_VTC(LW_) do { (void)hipFuncSetAttribute((const void *)k_v_tracers_explicit_column<LW_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
 	hipLaunchKernelGGL(k_v_tracers_explicit_column<LW_>, dim3((p.ncol + LW_ - 1) / LW_), dim3(64), lds, e->stream, p, e->nt, xin, xup, dt, ks, (const double *)e->d_ref); } while (0)
@@ -582,7 +583,8 @@ __global__ __launch_bounds__(128) void k_v_tracers_explicit_slide(KParams p, int
 int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt) {
 	if (e->nt == 0 || p.ncol == 0) return 0;
 	if (!e->opt_vt_column) {      // level-parallel / column-walking forms; option "vt_column": the one-lane-per-column LDS kernel, for A/B and tests
-		const size_t lds_slide = walk_lds_bytes(p.L);
+		const WalkShape shape = vwalk_shape(TMX_WALK_VT, p.L, e->opt_vt_walk, NTILES(e, p));
+		e->vwalk_launched[TMX_WALK_VT] = 0;      // (tmx_info(TMX_INFO_VERTICAL_KERNELS): the walk's segments, 0 every other form below)
 #if TMX_EXP
 		if (e->opt_vt_explicit_v1) {      // the form without LDS staging, for A/B and tests
 			dim3 blk(64, 4), grd(NTILES(e, p), (p.L + 3) / 4);
@@ -590,15 +592,16 @@ int tmxk_vi_tracers_explicit(tmx_engine * e, const KParams & p, const double * x
 				e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0, (const double *)e->d_ref);
 		} else
 #endif
-		if (e->opt_vt_walk < 0 && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column: -n = n segments per column
+		if (shape.nseg) {      // a thread walks (a segment of) its column: -n = n segments per column
 			const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
+			e->vwalk_launched[TMX_WALK_VT] = shape.nseg;
 			// default (-1000): segments in pairs (the two wavefronts of a workgroup) until the chip has two wavefronts per SIMD, at least five
 			// levels each -- ne30 L40 on one GPU: 1 350 tiles x 2 (measured: 1 / 2 / 3 / 4 segments 4.27 / 4.08 / 4.28 / 4.20 ms per step of BASELINE
 			// config 4's shape, the LDS-tiled kernel 4.67)
-			const int nseg = walk_segments(e->opt_vt_walk, nt_, p.L, 2048);
+			const int nseg = shape.nseg;
 			dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
 			const double ks_ = e->udiff ? e->cfg.uniform_diffusion_scalar : 0.0;
-			const size_t lds = lds_slide;
+			const size_t lds = shape.bytes;
 			for (int c0 = 0; c0 < e->nt; c0 += 3) {
 				const int ntr = std::min(3, e->nt - c0);
 #define LAUNCH_SLIDE(N_) do { if (p.closed) hipLaunchKernelGGL((k_v_tracers_explicit_slide<N_, true>), grd, blk, lds, e->stream, p, c0, xin, xup, dt, ks_, (const double *)e->d_ref, nt_, xm, nseg); \
@@ -876,9 +879,11 @@ __global__ __launch_bounds__(128) void k_vi_terms_explicit_slide(KParams p, cons
 
 void tmxk_vi_terms_explicit(tmx_engine * e, const KParams & p, const double * xin, double * xup, double dt, bool with_uv) {
 	const int nt_ = NTILES(e, p), xm = e->xcd_vertical;
-	const size_t lds_slide = walk_lds_bytes(p.L, TMX_RMTAB_DOUBLES);
-	if (e->opt_vite_walk < 0 && !with_uv && lds_slide <= 64 * 1024) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
-		const int nseg = walk_segments(e->opt_vite_walk, nt_, p.L + 1, 2048);
+	const WalkShape shape = vwalk_shape(TMX_WALK_VITE, p.L, e->opt_vite_walk, nt_, with_uv);
+	e->vwalk_launched[TMX_WALK_VITE] = shape.nseg;      // (tmx_info(TMX_INFO_VERTICAL_KERNELS): the walk's segments, 0 the level-parallel kernel below)
+	if (shape.nseg) {      // a thread walks (a segment of) its column; -n = n segments, -1000 = chosen from the grid size
+		const int nseg = shape.nseg;
+		const size_t lds_slide = shape.bytes;
 		dim3 blk(64, 2), grd(xcd_column_grid(xm, nt_, (nseg + 1) / 2));
 		const bool ud = e->udiff && e->fully_explicit;
 		const double z2 = e->cfg.ztop * e->cfg.ztop;

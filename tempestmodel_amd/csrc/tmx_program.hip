@@ -1010,6 +1010,7 @@ extern "C" int tmx_step(tmx_engine * e, int scheme, int first_step, int last_ste
 	const int need = scheme_instances(scheme);
 	REQUIRE(need > 0, TMX_ERR_INVALID, "unknown time scheme %d", scheme);
 	REQUIRE(e->cfg.n_instances >= need, TMX_ERR_INVALID, "time scheme %d needs %d data instances, engine has %d", scheme, need, e->cfg.n_instances);
+	if ((r = tmx_vertical_fit(e, tmx_vertical_fit_of_step(e)))) return r;      // a level count a vertical launcher of this configuration does not serve: refused before the step's first kernel
 	Program p;
 	if ((r = build_program(scheme, first_step, last_step, dt, p, e->strang_offc))) return r;
 	// Optional (TMX_GRAPH=1): single-rank steps replayed from a hipGraph -- the 20-30 launches of a step are

@@ -180,7 +180,7 @@ static int v_explicit_extras(tmx_engine * e, const KParams & p, int iinit, int i
 	if (!e->fully_explicit) return TMX_OK;
 	int r; if ((r = check_reference_state(e))) return r;
 	tmxk_vi_terms_explicit(e, p, inst(e, iinit), inst(e, iupd), dt, with_uv);
-	if (e->nt > 0)
+	if (e->nt > 0)      // (the caller has asked tmx_vertical_fit before its first kernel)
 		REQUIRE(tmxk_vi_tracers_explicit(e, p, inst(e, iinit), inst(e, iupd), dt) == 0, TMX_ERR_UNSUPPORTED,
 			"tracer column update: %d levels do not fit the LDS working set", e->L);
 	if (e->udiff && !uv_done)
@@ -276,6 +276,7 @@ bool stage_can_split(const tmx_engine * e) {
 // uniform diffusion, the fully explicit vertical mode (BASELINE config 4).
 int hv_stage(tmx_engine * e, int iinit, int ibase, int iupd, double dt, const double * lc, int nlc, bool split) {
 	StageTerms base;
+	int rf; if (e->fully_explicit && (rf = tmx_vertical_fit(e, TMX_FIT_VT_EXPLICIT))) return rf;      // refusal before the stage's first kernel
 	if (lc) REQUIRE(gather_terms(base, lc, nlc, iupd, 0u, WhereD{ e }), TMX_ERR_UNSUPPORTED, "linear combination with more than 11 source terms");
 	else base = base_terms(ibase, WhereD{ e });
 	auto kernels = [&](const KParams & p) { return hv_stage_kernels(e, p, iinit, iupd, dt, base); };
@@ -309,6 +310,7 @@ extern "C" int tmx_v_step_explicit(tmx_engine * e, int iinit, int iupd, double d
 	int r; if ((r = check_ready(e)) || (r = check_inst(e, iinit)) || (r = check_inst(e, iupd))) return r;
 	if (e->sw) return TMX_OK;      // VerticalDynamicsStub
 	REQUIRE(iinit != iupd, TMX_ERR_INVALID, "V StepExplicit: initial and update data instance must be distinct");
+	if (e->fully_explicit && (r = tmx_vertical_fit(e, TMX_FIT_VT_EXPLICIT))) return r;      // refusal before the first kernel: the update instance stays as it is
 	ProfScope ps(e, TMX_K_V_EXPLICIT);
 	if (udv_fused(e) && (r = check_reference_state(e))) return r;
 	tmxk_v_explicit(e, make_params(e), inst(e, iinit), inst(e, iupd), dt, udv_fused(e));
@@ -322,6 +324,8 @@ int v_step_implicit_impl(tmx_engine * e, int iinit, int iupd, double dt, int itb
 	int r; if ((r = check_ready(e)) || (r = check_inst(e, iinit)) || (r = check_inst(e, iupd))) return r;
 	if (e->sw) return TMX_OK;      // VerticalDynamicsStub
 	REQUIRE(dt != 0.0, TMX_ERR_INVALID, "StepImplicit: dt must be non-zero");
+	// refusal before the first kernel (the column solve rewrites the update instance; the tracer update follows it): the instance stays as it is
+	if ((r = tmx_vertical_fit(e, TMX_FIT_VI | TMX_FIT_VT))) return r;
 	KParams p = make_params(e);
 	const double * w0 = inst(e, iinit) + (size_t)TMX_SLAB_W(e->L, 0) * e->NS;
 	if (e->nt > 0 && iinit == iupd) {
@@ -679,6 +683,8 @@ extern "C" int tmx_v_step_implicit_terms_explicitly(tmx_engine * e, int iinit, i
 	int r; if ((r = check_ready(e)) || (r = check_inst(e, iinit)) || (r = check_inst(e, iupd))) return r;
 	REQUIRE(iinit != iupd && dt != 0.0, TMX_ERR_INVALID, "StepImplicitTermsExplicitly: distinct instances and non-zero dt required");
 	if (e->fully_explicit && (r = check_reference_state(e))) return r;
+	// refusal before the first kernel (the terms kernel rewrites the update instance; the tracer update follows it): the instance stays as it is
+	if ((r = tmx_vertical_fit(e, e->fully_explicit ? TMX_FIT_VT_EXPLICIT : TMX_FIT_VT_ALL))) return r;
 	ProfScope ps(e, TMX_K_VI_ASSEMBLE);
 	tmxk_vi_terms_explicit(e, make_params(e), inst(e, iinit), inst(e, iupd), dt, false);
 	if (e->nt > 0) {

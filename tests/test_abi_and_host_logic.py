@@ -310,8 +310,10 @@ def test_column_kernel_and_variant_info_before_any_launch():
     """tmx_info(TMX_INFO_COLUMN_KERNEL) and TMX_INFO_COLUMN_VARIANT (pairs per workgroup | assembly wavefronts << 4 | ring rows << 8 of the
     column solve's last launch) are -1 on an engine that has launched nothing, and so are TMX_INFO_STAGE_KERNEL (the explicit stage's last
     launch: 0 level-parallel, walk = segments | terms << 8 | flags << 16) and TMX_INFO_HYPERVIS_KERNEL (0 k_hypervis, n = the walk with n
-    segments) and TMX_INFO_PHYSICS_KERNEL (the last Kessler / DCMIP2016 launch: family | pbl << 2 | prec << 3 | kt or LDS bytes << 4); the enum
-    in the header ends with the five, at the indices the GPU tests and bench.py use; an index past the enum is -1 as well.  Plan-only engine: no device needed."""
+    segments) and TMX_INFO_PHYSICS_KERNEL (the last Kessler / DCMIP2016 launch: family | pbl << 2 | prec << 3 | kt or LDS bytes << 4),
+    TMX_INFO_TRACER_COLUMN_KERNEL (the implicit tracer column kernel: row lanes | log2 columns << 8 | all columns << 16) and
+    TMX_INFO_VERTICAL_KERNELS (the three explicit-mode vertical kernels, 12 bits each: 0 level-parallel, n segments); the enum in the header
+    ends with the seven, at the indices the GPU tests and bench.py use; an index past the enum is -1 as well.  Plan-only engine: no device needed."""
     import re
     from tempestmodel_amd import engine as eng
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -320,7 +322,8 @@ def test_column_kernel_and_variant_info_before_any_launch():
     names = re.findall(r"^\s*(TMX_INFO_[A-Z_0-9]+)", body[:body.index("};")], re.M)
     assert names.index("TMX_INFO_COLUMN_KERNEL") == 20 and names.index("TMX_INFO_COLUMN_VARIANT") == 21, names
     assert names.index("TMX_INFO_STAGE_KERNEL") == 22 and names.index("TMX_INFO_HYPERVIS_KERNEL") == 23, names
-    assert names.index("TMX_INFO_PHYSICS_KERNEL") == 24 and len(names) == 25, names
+    assert names.index("TMX_INFO_PHYSICS_KERNEL") == 24, names
+    assert names.index("TMX_INFO_TRACER_COLUMN_KERNEL") == 25 and names.index("TMX_INFO_VERTICAL_KERNELS") == 26 and len(names) == 27, names
     lib = eng.load_library()
     cfg = eng.TmxConfig()
     cfg.abi_version = eng.TMX_ABI_VERSION
@@ -330,7 +333,7 @@ def test_column_kernel_and_variant_info_before_any_launch():
     h = ctypes.c_void_p()
     assert lib.tmx_create(ctypes.byref(cfg), ctypes.byref(h)) == 0
     try:
-        assert [lib.tmx_info(h, k) for k in (20, 21, 22, 23, 24, 25)] == [-1, -1, -1, -1, -1, -1]
+        assert [lib.tmx_info(h, k) for k in (20, 21, 22, 23, 24, 25, 26, 27)] == [-1] * 8
     finally:
         lib.tmx_destroy(h)
 
