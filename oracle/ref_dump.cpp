@@ -271,7 +271,7 @@ int main(int argc, char ** argv) {
 	std::string mode = "steps", out = "", scheme = "ars343", pert = "exp", tcase = "jw";
 	int ne = 4, levels = 10, nsteps = 3, npatch = 6, nwarm = 0, geom = 1, every = 1, ntracers = 0, hvorder = 4;
 	double dt = 200.0, ztop = 30000.0, planet = 1.0, udiffS = 0.0, udiffV = 0.0;
-	bool fExplicitVertical = false, fZtopGiven = false;
+	bool fExplicitVertical = false, fZtopGiven = false, fLastStepFlag = false;
 	std::string physics = "none", vmethod = "v1";
 	double nuArg = -1.0, moisten = 0.0, offCentering = 0.0;
 	for (int i = 1; i < argc; i++) {
@@ -301,6 +301,7 @@ int main(int argc, char ** argv) {
 		else if (a == "--planet") { planet = atof(v); i++; }          // reduced-planet factor X (with --udiff)
 		else if (a == "--udiff") { udiffS = atof(v); udiffV = atof((i + 2 < argc) ? argv[i+2] : "0"); i += 2; }   // uniform diffusion K_scalar K_vector
 		else if (a == "--explicitvertical") { fExplicitVertical = true; }
+		else if (a == "--last-step") { fLastStepFlag = true; }        // --mode steps: fLastStep = true on the final step, as Model::Go passes it (Model.cpp:402-412)
 		else { fprintf(stderr, "unknown arg %s\n", a.c_str()); return 2; }
 	}
 
@@ -647,7 +648,7 @@ try {
 
 	} else if (mode == "steps") {
 		for (int s = 0; s < nsteps; s++) {
-			pTS->Step((s == 0) && (nwarm == 0), false, time, dt);
+			pTS->Step((s == 0) && (nwarm == 0), fLastStepFlag && s == nsteps - 1, time, dt);
 			time += timeDeltaT;
 			if (pPhysics) pPhysics->Perform(time);
 			if (((s + 1) % every == 0) || (s == nsteps - 1)) {

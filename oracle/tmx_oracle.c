@@ -1578,6 +1578,7 @@ int orc_step_ars343(const orc_grid * g, orc_state * s, double dt) {
 /* update -= dt * F(initial) on every interior column                                          */
 
 void orc_v_step_implicit_terms_explicitly(const orc_grid * g, orc_state * s, int iinit, int iupd, double dt) {
+	if (g->shallow_water) return;      /* VerticalDynamicsStub inherits the empty VerticalDynamics::StepImplicitTermsExplicitly (VerticalDynamics.h:89-95) */
 	const int L = g->L;
 	const int n = FTOT * (L + 1);
 	double * x0 = dalloc(n), * F = dalloc(n), * AB = dalloc(n * LDAB);

@@ -682,6 +682,7 @@ bool hypervis_active(const tmx_engine * e) {
 extern "C" int tmx_v_step_implicit_terms_explicitly(tmx_engine * e, int iinit, int iupd, double dt) {
 	int r; if ((r = check_ready(e)) || (r = check_inst(e, iinit)) || (r = check_inst(e, iupd))) return r;
 	REQUIRE(iinit != iupd && dt != 0.0, TMX_ERR_INVALID, "StepImplicitTermsExplicitly: distinct instances and non-zero dt required");
+	if (e->sw) return TMX_OK;      // VerticalDynamicsStub inherits the empty VerticalDynamics::StepImplicitTermsExplicitly (VerticalDynamics.h:89-95)
 	if (e->fully_explicit && (r = check_reference_state(e))) return r;
 	// refusal before the first kernel (the terms kernel rewrites the update instance; the tracer update follows it): the instance stays as it is
 	if ((r = tmx_vertical_fit(e, e->fully_explicit ? TMX_FIT_VT_EXPLICIT : TMX_FIT_VT_ALL))) return r;

@@ -13,6 +13,8 @@ The fixtures are data only: inputs and outputs of the reference's hot-path calls
   steps_ark232_tracers_ne2_L5_p6.npz   ARK232 with 2 tracers (StepImplicitTermsExplicitly + tracer column update): steps 1 and 3
   strang_variants_ne2_L4_p6.npz   Strang with ForwardEuler / RK4 / SSP3 / SSPRK53 and with off-centering: steps 1 and 3
   sw2_ne8_strang.npz      Williamson shallow-water test 2 (BASELINE config 1): state after 0, 1, 10 Strang steps
+  sw2_ne1_ark232.npz      the same test at one element per panel under ARK232 (the vertical stub's empty StepImplicitTermsExplicitly): steps 0..3
+  strang_last_step_ne2_L4_p6.npz   Strang / KGU35 ending with fLastStep = true (--last-step): state and carried instance after steps 2 and 3
   percall_schar_ne3_L6_p6.npz / steps_schar_ne3_L6_p6.npz   Schar mountain, reduced-radius sphere, Rayleigh layer (row H7)
   percall_tracers_ne3_L6_p6.npz / steps_tracers_ne3_L6_p6.npz   JW + 2 tracer densities (rows H8, V8)
   steps_visc2_ne3_L5_p6.npz   three ARS343 steps with hyperviscosity order 2
@@ -204,12 +206,40 @@ def gen_ark232_tracers(tmp):
     save("steps_ark232_tracers_ne2_L5_p6.npz", rec)
 
 
+def gen_strang_last_step(tmp):
+    # TimestepSchemeStrang::Step with fLastStep (TimestepSchemeStrang.cpp:654-657: the closing LinearCombineData(m_dCarryoverFinal, 1)
+    # is left out), which Model::Go passes on the final step of every run (Model.cpp:402-412): default KGU35, ne2 L4, three steps, the
+    # third with the flag -- state and carried instance 1 after steps 2 (the input of the last step) and 3, own geometry
+    d, _ = run(["--mode", "steps", "--ne", "2", "--levels", "4", "--dt", "400", "--steps", "3", "--scheme", "strang", "--last-step",
+                "--geom", "1"], tmp)
+    drop = ("lon", "lat", "z_levels", "z_interfaces", "element_area_node", "element_area_redge", "a_nodes", "b_nodes")
+    rec = {k: v for k, v in d.items() if not k.startswith(("state/", "checksum/")) and k.split("/")[-1] not in drop}
+    rec.update({k: v for k, v in compact_states(d, 6).items() if k.split("/")[1].split("_")[0] in ("step2", "step3")})
+    save("strang_last_step_ne2_L4_p6.npz", rec)
+
+
+SW_ARK232_NE = 1      # the smallest resolution the reference accepts for Williamson test 2 (one element per panel)
+
+
+def gen_sw_ark232(tmp):
+    # ARK232 with the shallow-water equation set: VerticalDynamicsStub inherits the empty StepImplicitTermsExplicitly
+    # (VerticalDynamics.h:89-95), so the stage is a copy and a DSS.  Williamson test 2, three steps from the analytic state
+    d, _ = run(["--case", "sw2", "--mode", "steps", "--ne", str(SW_ARK232_NE), "--dt", "200", "--steps", "3", "--scheme", "ark232",
+                "--geom", "0"], tmp)
+    rec = {k: v for k, v in d.items() if k.startswith("cfg/") or k.startswith("checksum/")}
+    for k, v in d.items():
+        if k.startswith("state/") and k.endswith("/node"):
+            rec[k] = v[:, 1:-1, 1:-1]
+    save("sw2_ne%d_ark232.npz" % SW_ARK232_NE, rec)
+
+
 def main():
     tmp = "/tmp/tmx_golden.tmxd"
-    if len(sys.argv) > 1:       # regenerate only the named fixtures: supercell, kessler, heldsuarez, strang
+    if len(sys.argv) > 1:       # regenerate only the named fixtures: supercell, kessler, heldsuarez, strang, ...
         for nm in sys.argv[1:]:
             {"supercell": lambda: gen_supercell(tmp), "kessler": gen_kessler_columns, "heldsuarez": lambda: gen_heldsuarez(tmp),
-             "strang": lambda: gen_strang_variants(tmp), "ark232_tracers": lambda: gen_ark232_tracers(tmp)}[nm]()
+             "strang": lambda: gen_strang_variants(tmp), "ark232_tracers": lambda: gen_ark232_tracers(tmp),
+             "strang_last_step": lambda: gen_strang_last_step(tmp), "sw_ark232": lambda: gen_sw_ark232(tmp)}[nm]()
         os.remove(tmp) if os.path.exists(tmp) else None
         return
     drop = ("lon", "lat", "z_levels", "z_interfaces", "element_area_node", "element_area_redge",
@@ -323,6 +353,8 @@ def main():
     gen_heldsuarez(tmp)
     gen_strang_variants(tmp)
     gen_ark232_tracers(tmp)
+    gen_strang_last_step(tmp)
+    gen_sw_ark232(tmp)
 
     # reference stdout known answers (same command as SURVEY.md section 8c)
     _, ka = run(["--mode", "steps", "--ne", "4", "--levels", "10", "--dt", "200", "--steps", "3",

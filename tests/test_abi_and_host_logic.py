@@ -223,6 +223,12 @@ def test_stepper_programs_share_the_copies_in_front_of_a_stub_implicit_step():
         assert run("ars343", 2, steps, 1) == (0, 3)
         assert run("ars343", 2, steps, 0) == (3, 0)
     assert run("ars232", 1, 3, 1) == (2, 2)
+    # ARK232 in shallow water (its StepImplicitTermsExplicitly is the stub's empty call on the device, its V.StepImplicit a no-op): of the
+    # six plain copies -- those in front of H are part of their stages -- two write the model state and three are updated in place by the
+    # DSS behind them: made; Copy(7 -> 2) in front of StepAfterSubCycle is never read again and shares
+    for steps in (1, 2, 5):
+        assert run("ark232", 2, steps, 1) == (5, 1)
+        assert run("ark232", 2, steps, 0) == (6, 0)
     # implicit vertical dynamics: the column solve rewrites rho*theta, W, rho of the copy; its U,V slabs are shared instead of copied
     for steps in (1, 2, 5):
         assert run("ars343", 0, steps, 1) == (0, 3)

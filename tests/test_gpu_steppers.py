@@ -164,7 +164,8 @@ def test_viscosity_order_2_steps():
 
 
 def test_graph_replay_is_bit_identical(monkeypatch):
-    """TMX_GRAPH=1: ARS343 and Strang steps replayed from a captured hipGraph equal the plain launch sequence bit for bit."""
+    """TMX_GRAPH=1: ARS343 steps replayed from a captured hipGraph equal the plain launch sequence bit for bit.  (ARS343 alone: the other
+    nine schemes, Strang's first / middle / last programs among them, replay against the oracle in tests/test_gpu_scheme_matrix.py.)"""
     from tempestmodel_amd.engine import Engine
     g, st = gu.make_grid(4, 8, 6)
     res = []
